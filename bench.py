@@ -17,6 +17,14 @@ clock (max) and the accepted count.  value = 1M * steps / max-over-ranks wall
 time of the timed region.  --scaling weak gives every rank its own 1M reads.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5|c5w]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR writes the per-read results of the last timed step as
+DIR/<field>.npy.  --full adds the legs that take runs of their own after the
+timed steps: the oracle parity of the timed rows, the CPU baseline on a sample
+(--cpu-sample, --cpu-kind) and the end-to-end imsame CLI run (--e2e); without
+it the line's "parity", "cpu_baseline" and "e2e" are null.
 """
 import argparse
 import ctypes as C
@@ -128,6 +136,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs with runs of their own: oracle parity of the timed "
+                         "rows + CPU baseline (--cpu-sample) and the end-to-end CLI run (--e2e); off: those are null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the per-read results of the last timed step as DIR/<field>.npy (see dump_outputs)")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2",
                     help="BASELINE.json workload (c2 = the metric's config; c3/c5/c5w are stress runs)")
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
@@ -139,7 +152,7 @@ def parse():
     ap.add_argument("--record-bp", type=int, default=None)
     ap.add_argument("--n-threads", type=int, default=16, help="reference -n_threads semantics")
     ap.add_argument("--cpu-sample", type=int, default=None,
-                    help="reads in the CPU baseline sample (0: skip; default: the config's)")
+                    help="--full: reads in the CPU baseline sample (0: skip; default: the config's)")
     ap.add_argument("--cpu-threads", type=int, default=None,
                     help="threads of the CPU baseline (default: the host cores this process may use)")
     ap.add_argument("--cpu-kind", choices=("auto", "port", "reference"), default="auto",
@@ -148,7 +161,7 @@ def parse():
                     help="search the database in slices of at most this many bases, one slice's index in HBM "
                          "at a time (imsame_dev_align_sliced; the index rebuilds are inside the timed step)")
     ap.add_argument("--e2e", choices=("auto", "on", "off"), default="auto",
-                    help="end-to-end imsame CLI run (parse, index, align, render, write) after the timed steps "
+                    help="--full: end-to-end imsame CLI run (parse, index, align, render, write) after the timed steps "
                          "(auto: on for c2 at N=1)")
     ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl",
                     help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo: rehearsal on one card)")
@@ -168,6 +181,8 @@ def parse():
     ap.add_argument("--traffic-json", default=None, help="PMC bytes per cell (default profiles/nw_traffic[_CONFIG].json)")
     ap.add_argument("--valu-json", default=None, help="PMC VALU per cell (default profiles/nw_valu[_CONFIG].json)")
     a = ap.parse_args()
+    if not a.full and (a.e2e == "on" or (a.cpu_sample or 0) > 0):
+        ap.error("--e2e on and --cpu-sample N > 0 ask for legs that run only with --full")
     cfg = CONFIGS[a.config]
     for k in ("reads", "read_len", "ref_bp", "record_bp", "cpu_sample"):
         if getattr(a, k) is None:
@@ -440,8 +455,12 @@ def main():
         roofline = dict({"bound": "hbm", "achieved": hbm["contract_achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": hbm["contract_frac"]}, **common, valu=None, hbm=hbm)
 
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, res, rank, world)
+
+    # --full only: the legs below take runs of their own (oracle, CPU baseline, CLI)
     cpu = parity = None
-    if rank == 0 and world == 1 and a.cpu_sample > 0:
+    if a.full and rank == 0 and world == 1 and a.cpu_sample > 0:
         # the oracle as the checker: the timed run's own rows on three windows
         parity = timed_parity(ref, rst, q, qs, res, lo, hi, a, params)
         if a.slice_bases:
@@ -449,7 +468,7 @@ def main():
         cpu = cpu_baseline(dev, ref, rst, q, qs, a, params)
 
     e2e = None
-    if rank == 0 and world == 1 and (a.e2e == "on" or (a.e2e == "auto" and a.config == "c2")):
+    if a.full and rank == 0 and world == 1 and (a.e2e == "on" or (a.e2e == "auto" and a.config == "c2")):
         dev.close()                                 # the CLI opens the device itself
         e2e = run_e2e(ref, rst, q, qs, a)
 
@@ -513,6 +532,31 @@ def main():
     rpin.free()
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_MAX_ROWS = 900_000        # x 64 bytes per sampled row (below) = 57.6 MB
+
+
+def dump_outputs(out_dir, res, rank, world):
+    """--dump-outputs: what a caller of the timed path receives from its last
+    timed step -- the per-read result rows (imsame_read_result) -- one array
+    per parity field as DIR/<field>.npy (DIR/<field>_rank<r>.npy with several
+    ranks, each its own shard).  db_seq and score (64-bit in the ABI) are
+    written as float64, the 32-bit fields as float32; every value the
+    benchmark's configurations produce is far below 2^24, so both are exact.
+    Up to 1M rows are written whole (56 MB); of more, a fixed sample of
+    DUMP_MAX_ROWS rows (PCG64, seed 0, ascending) with their row numbers in
+    rows.npy, so two builds write the same rows."""
+    from imsame_amd import PARITY_FIELDS
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    if len(res) > 1_000_000:
+        rows = np.sort(np.random.default_rng(0).choice(len(res), DUMP_MAX_ROWS, replace=False))
+        np.save(os.path.join(out_dir, f"rows{sfx}.npy"), rows.astype(np.float64))
+        res = res[rows]
+    for f in PARITY_FIELDS:
+        wide = res.dtype[f].itemsize == 8
+        np.save(os.path.join(out_dir, f"{f}{sfx}.npy"), res[f].astype(np.float64 if wide else np.float32))
 
 
 def nw_accounting(st, n_reads, parity):
