@@ -413,6 +413,10 @@ struct imsame_ctx {
     int nlanes = 1;                   // lanes of the running call (the seed scan's group size
                                       // follows the reads scanned across all of them)
     std::vector<uint32_t> part_paths; // host copy of this lane's paths for an imsame_dev_align_parts callback
+    // IMSAME_DEBUG_STALL (tests; read per call): microseconds of delay kernel
+    // ahead of every launch on [0] this lane's stream, [1] its stream_b, and
+    // how many the call enqueued (A's and B's host threads: atomic adds)
+    uint32_t stall_us[2] = {0, 0}, stall_n[2] = {0, 0};
 };
 
 static inline uint64_t hqs(const imsame_ctx *c, uint64_t r) { return c->hq[r - c->q_lo]; }
@@ -445,6 +449,47 @@ enum { C_NCAND = 0, C_NCAND2, C_NNEXT, C_NCANDB, C_NCAND2B, C_NNEXT2, C_WORKB,  
        C_WORK, C_WORK2, C_PATHS, C_FLAGS, C_ERR, C_HITS, C_CELLS, C_NACC, C_REDO,
        C_PROF, C_WIN = C_PROF + 12, C_FBK, C_SWORK, C_DBG = C_SWORK + 3, C_WASTE = C_DBG + 8,
        C_NSLOTS };
+
+// IMSAME_DEBUG_STALL=A:<us>|B:<us>[,...] (tests of the order between a lane's
+// two streams): a delay kernel ahead of every kernel launch of align_one on
+// the named side -- A the lane's own stream, B its stream_b / stream_bh
+// (pipeline B, round 1b's scan, the second half of a split round) -- so "this
+// side runs late" is a condition a test sets instead of a matter of timing.
+// One wave that touches no memory and waits on the constant-rate clock
+// (100 MHz); the iteration bound ends it whatever the clock does (each
+// iteration sleeps <= 2048 shader cycles: ~1 s at most).  <us> <= 20000.
+// Unset: no launch, no sync.  The CPU emulator has no streams and ignores it.
+#define STALL_US_MAX 20000u
+__global__ void __launch_bounds__(64) stall_kernel(uint32_t ticks) {
+    const uint64_t t0 = wall_clock64();
+    for (uint32_t i = 0; i < (1u << 20); ++i) {
+        if (wall_clock64() - t0 >= ticks) break;
+        __builtin_amdgcn_s_sleep(32);
+    }
+}
+static void stall_parse(imsame_ctx *c) {
+    c->stall_us[0] = c->stall_us[1] = 0;
+    c->stall_n[0] = c->stall_n[1] = 0;
+    const char *e = getenv("IMSAME_DEBUG_STALL");
+    while (e && *e) {
+        const int side = (*e == 'A' || *e == 'a') ? 0 : (*e == 'B' || *e == 'b') ? 1 : -1;
+        if (side >= 0 && e[1] == ':') {
+            const long us = strtol(e + 2, nullptr, 10);
+            c->stall_us[side] = (uint32_t)std::max<long>(0, std::min<long>(us, (long)STALL_US_MAX));
+        }
+        e = strchr(e, ',');
+        if (e) ++e;
+    }
+}
+static int stall(imsame_ctx *c, hipStream_t s) {
+    const int side = s == c->stream ? 0 : 1;
+    if (!c->stall_us[side]) return 0;
+    stall_kernel<<<1, 64, 0, s>>>(c->stall_us[side] * 100u);
+    HIPCHK(hipGetLastError());
+    __atomic_fetch_add(&c->stall_n[side], 1u, __ATOMIC_RELAXED);
+    return 0;
+}
+#define STALL(c, s) do { if (int src_ = stall((c), (s))) return src_; } while (0)
 
 static double now_ms() {
     struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -1391,6 +1436,7 @@ static int row_perm(imsame_ctx *c, const int32_t *crow, uint32_t n, uint32_t xca
     DBuf &cperm = qi ? c->cperm_b : c->cperm, &rhist = qi ? c->rhist_b : c->rhist;
     if (cperm.ensure((uint64_t)n * 4) || rhist.ensure((uint64_t)nb * 8)) return IMSAME_E_OOM;
     uint32_t *hist = rhist.as<uint32_t>(), *cur = hist + nb;
+    STALL(c, s);
     HIPCHK(hipMemsetAsync(hist, 0, (size_t)nb * 4, s));
     row_hist_kernel<<<std::min(nblk(n, 256), ROW_BLOCKS), 256, 0, s>>>(crow, n, nb, hist);
     row_scan_kernel<<<1, 1024, 0, s>>>(hist, nb, cur);
@@ -1459,6 +1505,7 @@ static int launch_nw(imsame_ctx *c, NwPlan &pl, const uint32_t *cread, const uin
     P.band_w = pl.band_w; P.redo = (uint32_t *)(ctr + C_REDO); P.win = (uint32_t *)(ctr + C_WIN);
     P.prof = getenv("IMSAME_NW_PROF") ? (unsigned long long *)(ctr + C_PROF) : nullptr;
     P.slot_bits = pl.np ? ao->slotbits.as<uint32_t>() : nullptr; P.slot_words = pl.slot_words;
+    STALL(c, s);                                 // (ahead of e0: not in the launch's time)
     HIPCHK(hipMemsetAsync(work, 0, 4, s));
     HIPCHK(hipEventRecord(e0, s));               // the launch's time includes its ordering
     auto win_params = [&] {
@@ -1629,6 +1676,12 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
         ~StreamSwap() { if (on) std::swap(c->stream_b, c->stream_bh); }
     } swap_b{c, pipes_on(n) && prio_b(c)};
     if (swap_b.on) std::swap(c->stream_b, c->stream_bh);
+    if (swap_b.on && getenv("IMSAME_DEBUG_ROUNDS")) fprintf(stderr, "[prio_b] stream_b is the high-priority stream\n");
+    stall_parse(c);
+    struct StallOff {                 // (launch_nw also serves imsame_dev_nw_pairs: no stall outside this call)
+        imsame_ctx *c;
+        ~StallOff() { c->stall_us[0] = c->stall_us[1] = 0; }
+    } stall_off{c};
     // this lane's bases (and the 16-byte chunk loads' reach past its last read)
     if (int rq = query_wait(c, s, hqs(c, read_to) + 64)) return rq;
     imsame_stats st;
@@ -1768,6 +1821,7 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
             const int L = RP.pick_L(rr ? rr : rnd, na);
             // (IMSAME_SEED_BLOCKS: at most this many blocks, the kernels stride)
             auto sb = [&](uint64_t lanes) { return std::min<unsigned>(nblk(lanes, 256), seed_blocks()); };
+            STALL(c, ss);
             HIPCHK(hipEventRecord(e0, ss));
             if (SL.ent_abs) {
                 if (L >= 64)      seed_group_kernel<64, SPEC_BIG, true><<<sb((uint64_t)na * 64), 256, SEED_LDS_BLOCK(64, SPEC_BIG), ss>>>(SL);
@@ -1822,6 +1876,7 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
                            (uint32_t *)(ctr + nnext_slot), (unsigned long long *)(ctr + C_CELLS),
                            (unsigned long long *)(ctr + C_NACC), (unsigned long long *)(ctr + C_ERR),
                            c->db_start.as<uint64_t>(), ctr + C_FLAGS, (unsigned long long *)(ctr + C_WASTE), uperm};
+            STALL(c, ss);
             update_kernel<<<std::min<unsigned>(nblk(nc, 256), upd_blocks()), 256, 0, ss>>>(U);
             POISON_SYNC(ss, "update_kernel", c);
             HIPCHK(hipGetLastError());
@@ -2339,6 +2394,8 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
                 (unsigned long long)hc[C_PROF + 7], (unsigned long long)hc[C_PROF + 8], (unsigned long long)hc[C_PROF + 9],
                 (unsigned long long)hc[C_PROF + 10], (unsigned long long)hc[C_PROF + 11]);
     }
+    if ((c->stall_us[0] || c->stall_us[1]) && getenv("IMSAME_DEBUG_ROUNDS"))
+        fprintf(stderr, "[stall] A=%u B=%u\n", c->stall_n[0], c->stall_n[1]);
     st.nw_launch_ms = st.nw_launches ? st.ms_nw / st.nw_launches : 0;
     st.nw_bytes = 2 * st.nw_cells;       // 2 B/cell traceback floor; bench.py adds xlen + ylen per NW
     int ret = IMSAME_OK;

@@ -389,6 +389,17 @@ __device__ __forceinline__ int32_t predicted_row(uint64_t raw, uint64_t ylen, in
                                                 bool weak_rows = false) {
     return (!weak_rows && weak_hit(raw, ylen)) ? INT32_MIN : (int32_t)(rec_pos - read_pos);
 }
+// Round 1's launch is cut in two by predicted row (imsame_dev.hip:align_one:
+// the unpredicted candidates run on the second pipeline's stream, the
+// predicted ones on the first's) and a read's update reads all its
+// candidates' results, so a read's candidates must all fall on one side.  A
+// read has more than one candidate in round 1 only by weak-first speculation
+// (spec_after_first); with IMSAME_NW_WEAK_ROWS its weak first hit would be
+// predicted and its other candidates not: such a read's entries are all
+// unpredicted.  (Without that knob a weak hit has no row anyway; a strong
+// first hit with several candidates occurs in later rounds only, whose
+// launches are whole.)
+__device__ __forceinline__ bool split_by_cut(bool first_weak, uint32_t ne) { return first_weak && ne > 1; }
 // Speculation from the first candidate on: a read whose first e-value pass is
 // weak (a random read's, by the idents quirk) will most likely see it
 // rejected, and its next passes too, so it emits up to spec_weak of them in
@@ -431,7 +442,7 @@ __device__ __forceinline__ void seed_one(const SeedLaunch &S, uint32_t idx, Seed
     uint32_t ne = 0, perr = 0;
     int32_t row0 = INT32_MIN;              // first candidate's diagonal (nw16 traceback window)
     uint32_t code = 0;
-    bool have = false, stop = false, paused = false;
+    bool have = false, stop = false, paused = false, weak0 = false;
     // A read that runs out of budget pauses at the hit it has not examined
     // and resumes there next round: the visiting order is unchanged, so this
     // only reshapes the work (reads that scan every window -- no true hit --
@@ -482,6 +493,7 @@ __device__ __forceinline__ void seed_one(const SeedLaunch &S, uint32_t idx, Seed
                 if (ne == 0) {
                     row0 = predicted_row(raw, ylen, ent_rel_t<ABS>(ent, xs), (int64_t)(p + 1 - rs), S.weak_rows);
                     spec = spec_after_first(S, spec, nm, raw, ylen);
+                    weak0 = weak_hit(raw, ylen);
                 }
                 emit[ne++] = sid;
                 if (ne == spec) {
@@ -514,7 +526,7 @@ __device__ __forceinline__ void seed_one(const SeedLaunch &S, uint32_t idx, Seed
     uint32_t *cr = shortc ? S.cread : S.cread2, *cs = shortc ? S.csid : S.csid2;
     for (uint32_t m = 0; m < ne; ++m) { cr[o + m] = (uint32_t)r; cs[o + m] = emit[m]; }
     if (shortc && S.crow)
-        for (uint32_t m = 0; m < ne; ++m) S.crow[o + m] = m ? INT32_MIN : row0;
+        for (uint32_t m = 0; m < ne; ++m) S.crow[o + m] = (m || split_by_cut(weak0, ne)) ? INT32_MIN : row0;
     S.cbase[k] = o; S.ccnt[k] = ne;
 }
 
@@ -740,7 +752,8 @@ __device__ void seed_group(const SeedLaunch &S, uint32_t gidx, int wl, int lane,
         const int64_t xe = (ent.y == S.n_db - 1) ? (int64_t)S.db_len : (int64_t)S.db_start[ent.y + 1] - 1;
         const uint64_t raw = ungapped_raw(tab, S.dbw, S.qw, ent_pos_t<ABS>(ent, xs), (int64_t)(rs + e0p) + 1, xs, xe, ys,
                                           ye, (int64_t)S.db_len, (int64_t)S.q_len);
-        S.crow[o] = predicted_row(raw, ylen, ent_rel_t<ABS>(ent, xs), (int64_t)e0p + 1, S.weak_rows);
+        S.crow[o] = split_by_cut(weak_hit(raw, ylen), ne)
+                        ? INT32_MIN : predicted_row(raw, ylen, ent_rel_t<ABS>(ent, xs), (int64_t)e0p + 1, S.weak_rows);
         for (uint32_t m = 1; m < ne; ++m) S.crow[o + m] = INT32_MIN;
     }
     S.cbase[k] = o; S.ccnt[k] = ne;

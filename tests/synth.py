@@ -179,3 +179,67 @@ def adversarial_long_pairs():
         (y7[3000:9000].copy(), y7),                                       # read longer than its record
     ]
     return [x.tobytes() for x, _ in pairs], [y.tobytes() for _, y in pairs]
+
+
+def adversarial_short_pairs(xl, yl):
+    """13 short-read pairs at one shape -- every read has yl bases, the
+    longest record xl -- built to push the packed int16 kernel's drifting
+    terms (nw16_kernel.hip, nw16_fits) to the ends of their range: scores
+    that only fall (no match anywhere), that climb 4 per row on the first or
+    last diagonal, a read that jumps from the record's head to its tail (one
+    gap of xl - yl), tandem and dinucleotide repeats (ties in every column
+    maximum), and short records beside long ones in one lockstep wave (rows
+    past a record's end are garbage the range proof covers)."""
+    rng = np.random.default_rng(177)
+    rnd = lambda n: ACGT[rng.integers(0, 4, n)]             # noqa: E731
+    full = lambda n, b: np.full(n, ord(b), np.uint8)        # noqa: E731
+    x = rnd(xl)
+    h = yl // 2
+    unit = rnd(7)
+    rep = np.tile(unit, xl // 7 + 2)
+    assert xl >= yl
+    x8 = np.concatenate([rnd(yl), full(xl - yl, "C")])
+    y8 = x8[:yl].copy()
+    y8[y8 == ord("C")] = ord("G")
+    ac = np.frombuffer(b"AC", dtype=np.uint8)
+    pairs = [
+        (full(xl, "A"), full(yl, "C")),                                        # 1 no match at all
+        (x, x[-yl:]),                                                          # 2 the record's tail
+        (x, x[:yl]),                                                           # 3 the record's head
+        (full(xl, "A"), full(yl, "A")),                                        # 4 every cell a match
+        (rnd(12), rnd(yl)),                                                    # 5 lockstep partner: garbage rows
+        (rnd(xl), rnd(yl)),                                                    # 6 unrelated
+        (rep[:xl], rep[3:3 + yl]),                                             # 7 tandem repeat, shifted by 3
+        (x8, y8),                                                              # 8 head with C -> G, then all C
+        (np.concatenate([full(xl // 2, "A"), full(xl - xl // 2, "C")]),
+         np.concatenate([full(h, "A"), full(yl - h, "C")])),                   # 9 two homopolymer halves
+        (np.tile(ac, xl // 2 + 1)[:xl], np.tile(ac, yl // 2 + 1)[:yl]),        # 10 dinucleotide
+        (x, np.concatenate([x[:h], x[len(x) - (yl - h):]])),                   # 11 head + tail: one long gap
+        (full(13, "A"), full(yl, "A")),                                        # 12 a 13-base record
+        (x[:yl].copy(), x[:yl].copy()),                                        # 13 identical, square
+    ]
+    assert all(len(b) == yl for _, b in pairs) and max(len(a) for a, _ in pairs) == xl
+    return [a.tobytes() for a, _ in pairs], [b.tobytes() for _, b in pairs]
+
+
+def nw16_limit_igap(K, xmax, ymax, egap):
+    """The strongest (most negative) open penalty the packed kernel's range
+    proof admits for K columns per lane, records <= xmax, reads <= ymax and
+    extension penalty egap -- nw16_kernel.hip:nw16_fits's documented bound
+    4 ycols + |ig| + |eg| (xmax + 64 + ycols + 2) + 16 <= 8191."""
+    ycols = -(-ymax // K) * K
+    return -(8191 - 16 - 4 * ycols - abs(egap) * (xmax + 64 + ycols + 2))
+
+
+# nw16 at the limit of its range proof: (id, environment, K the launch must
+# report, xmax, ymax, [(egap, igap at the limit), ...])
+NW16_LIMIT_CASES = [
+    ("k10_2000x160", {}, 10, 2000, 160, [(0, -7535), (-1, -5309), (-2, -3083), (-3, -857)]),
+    ("k5_2000x160", {"IMSAME_NW_K": "5"}, 5, 2000, 160, [(0, -7535), (-1, -5309), (-2, -3083), (-3, -857)]),
+    ("k3_2000x150", {"IMSAME_NW_K": "3"}, 3, 2000, 150, [(0, -7575), (-1, -5359), (-2, -3143), (-3, -927)]),
+    ("k10_2000x150", {"IMSAME_NW_K19": "0"}, 10, 2000, 150, [(0, -7575), (-1, -5359), (-2, -3143), (-3, -927)]),
+    ("k19_2000x150", {}, 19, 2000, 150, [(0, -7567), (-1, -5349), (-2, -3131), (-3, -913)]),
+    ("k19_700x150", {}, 19, 700, 150, [(-8, -223)]),
+    ("k10_300x160", {}, 10, 300, 160, [(-3, -5957), (-8, -3327)]),
+    ("k10_3000x31", {}, 10, 3000, 31, [(-1, -4909), (-2, -1803)]),
+]

@@ -1228,8 +1228,10 @@ def test_independent_pipelines_equal_joined_rounds(dev, oracle, shape, monkeypat
     (IMSAME_PIPES=0), with round 1's launch cut into its unpredicted and
     predicted candidates (default) or not (IMSAME_CUT_WEAK=0); the default run
     equals the oracle on three windows; a third of the reads are random (many
-    later rounds on both pipelines), and IMSAME_SPEC=2 / IMSAME_SPEC_WEAK=8
-    squeeze the pipelines' list parts."""
+    later rounds on both pipelines), IMSAME_SPEC=2 / IMSAME_SPEC_WEAK=8
+    squeeze the pipelines' list parts, and with IMSAME_NW_WEAK_ROWS=1 weak
+    first hits predict rows (a weak read's candidates must still fall on one
+    side of the cut: seed_kernel.hip:split_by_cut)."""
     n = 125_000 if shape == "shard" else 400_000
     ref, rst = synth.make_reference_arr(8_000_000, 2_000, seed=91)
     q, qs = synth.make_reads_arr(ref, n, 150, seed=92, frac_true=0.67, ins=0.002, dele=0.002)
@@ -1240,7 +1242,8 @@ def test_independent_pipelines_equal_joined_rounds(dev, oracle, shape, monkeypat
     monkeypatch.setenv("IMSAME_PIPES", "1")           # (by default only lanes of >= 200k reads)
     monkeypatch.setenv("IMSAME_DEBUG_ROUNDS", "1")
     res = None
-    for env in [{}, {"IMSAME_CUT_WEAK": "0"}, {"IMSAME_SPEC": "2", "IMSAME_SPEC_WEAK": "8"}]:
+    for env in [{}, {"IMSAME_CUT_WEAK": "0"}, {"IMSAME_SPEC": "2", "IMSAME_SPEC_WEAK": "8"},
+                {"IMSAME_NW_WEAK_ROWS": "1"}]:
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         r, pp, st = dev.align(n_threads=16, want_paths=True)
@@ -1262,3 +1265,57 @@ def test_independent_pipelines_equal_joined_rounds(dev, oracle, shape, monkeypat
     assert rc == 0
     for (a, b), e in zip(wins, exp):
         assert not _cmp(res[a:b], e), ((a, b), _cmp(res[a:b], e))
+
+
+_NW_FIELDS = ("score", "bx", "by", "length", "identities", "igaps", "egaps", "head_x", "head_y")
+
+
+@pytest.mark.parametrize("cid,env,K,xmax,ymax,gaps", synth.NW16_LIMIT_CASES, ids=[c[0] for c in synth.NW16_LIMIT_CASES])
+def test_nw16_at_range_limit(dev, oracle, cid, env, K, xmax, ymax, gaps, monkeypatch, capfd):
+    """nw16_kernel.hip keeps two candidates' scores as int16 halves of one
+    register; nw16_fits (R <= 8191) is what makes that exact.  Each column
+    form (3, 5, 10, 19: their own ycols, checkpoint interval and padding
+    columns) runs synth.adversarial_short_pairs at the strongest open penalty
+    the proof admits for its shape and extension penalty (synth.NW16_LIMIT_CASES),
+    two-pass, one-pass and on the int32 kernel: all nine NW fields equal the
+    oracle's, accepted pairs' text too, and the launch's diagnostics line
+    names the expected form (a shape that silently took the int32 kernel
+    fails).  One step past the limit the form does not run (the 19-column
+    shape then fits the 10-column form, whose ycols are 150; every other
+    shape goes to the int32 kernel) and the rows still equal the oracle's."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    monkeypatch.setenv("IMSAME_NW_PROF", "1")
+    X, Y = synth.adversarial_short_pairs(xmax, ymax)
+
+    def run(ig, eg, flags):
+        p = dev.params(igap=ig, egap=eg, min_coverage=1e-9, min_identity=1e-9, flags=flags)
+        capfd.readouterr()
+        res, paths, _ = dev.nw_pairs(X, Y, p, want_paths=True)
+        err = capfd.readouterr().err
+        ks = [int(l.split()[l.split().index("k") + 1]) for l in err.splitlines() if l.startswith("[nwprof-raw]")]
+        return res, paths, ks
+
+    for eg, ig in gaps:
+        assert synth.nw16_limit_igap(K, xmax, ymax, eg) == ig
+        exp = [oracle.nw(x, y, igap=ig, egap=eg, text=True) for x, y in zip(X, Y)]
+        n_text = 0
+        for mode, flags in (("two-pass", 0), ("one-pass", FLAG_NW16_ONEPASS), ("nw32", FLAG_NW32)):
+            res, paths, ks = run(ig, eg, flags)
+            assert ks == ([] if mode == "nw32" else [K]), (cid, mode, ig, eg, ks)
+            for k, o in enumerate(exp):
+                for f in _NW_FIELDS:
+                    assert int(res[k][f]) == int(o[f]), (cid, mode, f, k, ig, eg)
+                if res[k]["status"] == 1:
+                    txt, ident = render(X[k], Y[k], res[k],
+                                        paths[res[k]["path_off"]:res[k]["path_off"] + res[k]["path_len"]])
+                    assert txt == o["text"] and ident == o["identities"], (cid, mode, k, ig, eg)
+                    n_text += 1
+        assert n_text >= 3 * 4, (cid, ig, eg, n_text)
+        # one step past the limit
+        res, _, ks = run(ig - 1, eg, 0)
+        assert ks == ([10] if K == 19 else []), (cid, ig - 1, eg, ks)
+        for k, (x, y) in enumerate(zip(X, Y)):
+            o = oracle.nw(x, y, igap=ig - 1, egap=eg, text=False)
+            for f in _NW_FIELDS:
+                assert int(res[k][f]) == int(o[f]), (cid, "past", f, k, ig - 1, eg)

@@ -782,3 +782,32 @@ def test_render_of_emulated_paths_matches_reference_text(emu, oracle):
         assert ident == r["identities"]
         n += 1
     assert n > 20
+
+
+@pytest.mark.parametrize("cid,env,K,xmax,ymax,gaps", synth.NW16_LIMIT_CASES, ids=[c[0] for c in synth.NW16_LIMIT_CASES])
+def test_emulated_nw16_at_range_limit(emu, oracle, cid, env, K, xmax, ymax, gaps, monkeypatch):
+    """The emulated twin of test_gpu.py:test_nw16_at_range_limit: the packed
+    int16 kernel's source, in each column form, on synth.adversarial_short_pairs
+    at the strongest open penalty nw16_fits admits (synth.NW16_LIMIT_CASES,
+    checked against the documented bound) -- all nine NW fields equal the
+    oracle's, two-pass and one-pass; the 19- and 3-column forms are proven by
+    their launch counters.  With this green, a failure of the GPU test points
+    at the compiled kernel."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    k19, k3 = emu.lib.emu_k19_count, emu.lib.emu_k3_count
+    k19.restype = k3.restype = C.c_uint32
+    X, Y = synth.adversarial_short_pairs(xmax, ymax)
+    for eg, ig in gaps:
+        assert synth.nw16_limit_igap(K, xmax, ymax, eg) == ig
+        exp = [oracle.nw(x, y, igap=ig, egap=eg, text=False) for x, y in zip(X, Y)]
+        for one in (False, True):
+            p = oracle.params(igap=ig, egap=eg, want_paths=1, min_coverage=1e-9, min_identity=1e-9,
+                              flags=imsame_amd.FLAG_NW16_ONEPASS if one else 0)
+            k19(), k3()
+            rc, res, _, fl = emu.nw_pairs(X, Y, p, paths_cap=16 * (xmax + ymax))
+            assert rc == 0 and fl == 0, (cid, ig, eg, one, rc, fl)
+            assert ((k19() > 0), (k3() > 0)) == (K == 19, K == 3), (cid, ig, eg, one)
+            for k, o in enumerate(exp):
+                for f in ("score", "bx", "by", "length", "identities", "igaps", "egaps", "head_x", "head_y"):
+                    assert int(res[k][f]) == int(o[f]), (cid, one, f, k, ig, eg)
