@@ -59,7 +59,7 @@ __global__ void mark_record_starts(const uint64_t *st, uint64_t n, uint64_t L, u
 // the 2-bit packed bases (seed_kernel.hip:pk_word): words [w0, w1) of dst
 // (biased: dst[w] holds bases 16w ..) from src (biased: src[p] = base p,
 // valid for lo <= p < hi; other slots 0)
-// ... and, where `bad` is given, bit 0 of *bad set if a byte of [lo, hi) in
+// ... and, where `bad` is given, bit 3 (8) of *bad set if a byte of [lo, hi) in
 // these words is not 'A', 'C', 'G' or 'T': the 2-bit codes (and nw16's
 // base_code) alias every other byte to one of them, so the bases must be what
 // IMSAME's loaders keep (IMSAME.c:216-221, :340-345; include/imsame_dev.h)
