@@ -447,7 +447,7 @@ static inline const uint64_t *dev_qs(const imsame_ctx *c) {
 // counters block layout (u64 slots)
 enum { C_NCAND = 0, C_NCAND2, C_NNEXT, C_NCANDB, C_NCAND2B, C_NNEXT2, C_WORKB,   // (round 1b: B, 2)
        C_WORK, C_WORK2, C_PATHS, C_FLAGS, C_ERR, C_HITS, C_CELLS, C_NACC, C_REDO,
-       C_PROF, C_WIN = C_PROF + 12, C_FBK, C_SWORK, C_DBG = C_SWORK + 3, C_WASTE = C_DBG + 8,
+       C_PROF, C_WIN = C_PROF + 14, C_FBK, C_SWORK, C_DBG = C_SWORK + 3, C_WASTE = C_DBG + 8,
        C_NSLOTS };
 
 // IMSAME_DEBUG_STALL=A:<us>|B:<us>[,...] (tests of the order between a lane's
@@ -2389,10 +2389,11 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
         const double ghz = hc[C_PROF + 5] ? tot / (double)hc[C_PROF + 5] * 0.1 : 0.0;
         fprintf(stderr, "[nwprof] setup %.3f sweep1 %.3f reduce %.3f sweep2 %.3f walk %.3f (fractions of %.4g wave-cycles) "
                 "clock_ghz %.3f best_cells(weak: last_row last_col<=40 <=200 higher | predicted: in out) "
-                "%llu %llu %llu %llu | %llu %llu\n", hc[C_PROF] / tot, hc[C_PROF + 1] / tot, hc[C_PROF + 2] / tot,
+                "%llu %llu %llu %llu | %llu %llu weak_window_waves(all skipped_second_sweep) %llu %llu\n", hc[C_PROF] / tot, hc[C_PROF + 1] / tot, hc[C_PROF + 2] / tot,
                 hc[C_PROF + 3] / tot, hc[C_PROF + 4] / tot, tot, ghz, (unsigned long long)hc[C_PROF + 6],
                 (unsigned long long)hc[C_PROF + 7], (unsigned long long)hc[C_PROF + 8], (unsigned long long)hc[C_PROF + 9],
-                (unsigned long long)hc[C_PROF + 10], (unsigned long long)hc[C_PROF + 11]);
+                (unsigned long long)hc[C_PROF + 10], (unsigned long long)hc[C_PROF + 11],
+                (unsigned long long)hc[C_PROF + 12], (unsigned long long)hc[C_PROF + 13]);
     }
     if ((c->stall_us[0] || c->stall_us[1]) && getenv("IMSAME_DEBUG_ROUNDS"))
         fprintf(stderr, "[stall] A=%u B=%u\n", c->stall_n[0], c->stall_n[1]);

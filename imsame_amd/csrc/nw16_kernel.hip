@@ -111,7 +111,12 @@ __host__ __device__ constexpr int nw16_nrec(int K) { return K <= 8 ? 2 : K <= 10
 #define NW16_WIN_UP 32            // window rows above the predicted first row
 #define NW16_WIN_DOWN 24          // ... and below the predicted last row
 #define NW16_WIN_MAX 448          // longest window (steps) a wave writes in its first sweep
-#define NW16_WIN_BOTTOM 40        // rows above the last one for an unpredicted candidate
+// Rows above the last one that an UNPREDICTED candidate's wave writes in its
+// first sweep; < 0 (the default): none.  A wave is spared the second sweep
+// only if all its 16 halves walk inside the window, and with 40 rows 46 of
+// 14,058 such waves did at C2, 141 of 144,800 at C3 (P.prof [12], [13]): the
+// ~48 traceback steps per task bought nothing.  IMSAME_NW_WIN_BOTTOM=N sets N.
+#define NW16_WIN_BOTTOM (-1)
 #define NW16_BAND2 4              // the second sweep's retry band, in bands
 
 // does the launch fit the int16 path?  (all gap terms non-positive)
@@ -336,21 +341,35 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
             }
         }
         const int xlp = max(xl[0], xl[1]);
+        int xmax = valid[0] ? xlp : 0, xmin = valid[0] ? min(xl[0], xl[1]) : INT_MAX;
+        for (int o = 32; o > 0; o >>= 1) {
+            xmax = max(xmax, wv_shfl_xor(xmax, o));
+            xmin = min(xmin, wv_shfl_xor(xmin, o));
+        }
+        // wave-uniform in SGPRs: the sweep's step counter and bounds are scalar
+        xmax = (int)wv_first((uint32_t)xmax); xmin = (int)wv_first((uint32_t)xmin);
         // an idle group (no candidate) reads group 0's record, so its lockstep
         // garbage stays a bounded DP like everyone else's
         uint8_t *X8 = wsm + (size_t)(valid[0] ? g : 0) * P.xstride;
         if (valid[0]) {
             // 16 rows per lane and iteration: one unaligned 16-byte load per record
             // where the chunk lies inside it (else bytes clamped to its last base),
-            // codes packed four per dword, one 16-byte LDS store (xstride is a
-            // multiple of 16, so the chunk past xlp stays inside the group's area)
-            const int nch = (xlp + 15) >> 4;
+            // codes packed four per dword, one 16-byte LDS store.  Every record is
+            // padded with its last code out to the WAVE's last row read, xmax + G
+            // (the lockstep rows a lane computes past its own record), so the sweep
+            // reads row i + 1 unclamped; xstride holds xcap + G + 1 rows rounded up
+            // to 16 (nw16_shape), so the last chunk stays inside the group's area
+            const int nch = (xmax + G + 1 + 15) >> 4;
             for (int c = gl; c < nch; c += G) {
                 const int k0 = c << 4;
                 uint32_t w[2][4];
                 for (int h = 0; h < 2; ++h) {
                     if (k0 + 16 <= xl[h]) {
                         __builtin_memcpy(w[h], Xg[h] + k0, 16);
+                    } else if (k0 >= xl[h]) {
+                        const uint32_t v = (uint32_t)Xg[h][xl[h] - 1] * 0x01010101u;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) w[h][q] = v;
                     } else {
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
@@ -371,13 +390,6 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
         }
         wv_lds_sync();
 
-        int xmax = valid[0] ? xlp : 0, xmin = valid[0] ? min(xl[0], xl[1]) : INT_MAX;
-        for (int o = 32; o > 0; o >>= 1) {
-            xmax = max(xmax, wv_shfl_xor(xmax, o));
-            xmin = min(xmin, wv_shfl_xor(xmin, o));
-        }
-        // wave-uniform in SGPRs: the sweep's step counter and bounds are scalar
-        xmax = (int)wv_first((uint32_t)xmax); xmin = (int)wv_first((uint32_t)xmin);
         // traceback window of the first sweep: steps [tw0, tw1), both odd (the
         // loops advance t by 2 from 1); rows [lo, hi] of every candidate's
         // prediction take steps lo .. hi + G - 1
@@ -463,20 +475,31 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
         uint32_t outT = A[K - 1], outMS = 0, outL = 0;
         const int tend = xmax - 1 + G;
         xrow = valid[0] ? X8[min(max(1 - gl, 0), xcl)] : 0u;
-        uint32_t bestC = pk1(-NW16_BIG) ^ NW16_H, bestCi = 0, ipk = pk1(1 - gl);
-        int bestR[2] = {INT_MIN, INT_MIN}, bestRj[2] = {0, 0};
+        // the column best and the STEP that took it (row + gl: the step is wave-uniform,
+        // so no per-lane row counter runs beside the sweep; never taken: row 0)
+        uint32_t bestC = pk1(-NW16_BIG) ^ NW16_H, bestCt = pk1(gl);
+        const uint32_t glpk = pk1(gl);
+        // the last row's best of each half goes straight to the reduction's slots
+        // (rowbest(): once per lane and half), not through registers kept over the sweep
+        for (int h = 0; h < 2; ++h) { red[lane * 8 + 4 * h + 0] = INT_MIN; red[lane * 8 + 4 * h + 1] = 0; }
         const uint32_t limp = pk2(xl[0] - 2, xl[1] - 2);
         uint8_t *tb3 = (uint8_t *)tbw;
 
-        auto step = [&](const bool PRE, const bool CAREFUL, const bool TB, const int t, uint32_t (&cur)[K],
-                        const uint32_t (&own)[K], uint32_t &in0, const uint32_t in1) {
+        // HEAD: some lane may be at a row <= 1 -- row 0 repeats (i < 1), row 1 has
+        // no up term and leaves mc frozen (:449, :476), the column best starts at
+        // row 1 -- or still above row -1 (its row read clamps at 0).
+        // TAIL: some lane may be past row xlen-2 of a half: the column best's upper
+        // row limit (rowbest() below takes the last row's best).
+        // Neither: every lane at rows 2 .. xlen-2 of both halves (the plain step).
+        auto step = [&](const bool HEAD, const bool TAIL, const bool TB, const int t, uint32_t (&cur)[K],
+                        const uint32_t (&own)[K], uint32_t &in0, const uint32_t in1) WV_LAMBDA_INLINE {
             const uint32_t sN = (uint32_t)wv_shr1((int)outT), mS = (uint32_t)wv_shr1((int)outMS),
                            mL0 = (uint32_t)wv_shr1((int)outL);
             const int i = t - gl;
             const Nw16Row xr = nw16_row(xrow);
-            xrow = CAREFUL ? X8[min(max(i + 1, 0), xcl)] : X8[i + 1];          // next row, read ahead
-            const bool pre = PRE && i < 1;
-            const bool row1 = CAREFUL && i <= 1;                     // up invalid, mc frozen (:449, :476)
+            xrow = HEAD ? X8[max(i + 1, 0)] : X8[i + 1];           // next row, read ahead (padded past the record)
+            const bool pre = HEAD && i < 1;
+            const bool row1 = HEAD && i <= 1;                        // up invalid, mc frozen (:449, :476)
             uint32_t mfS = mS, l0 = mL0;
             TbWords<K> tw = {};
 #pragma unroll
@@ -509,30 +532,42 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
             // rows outside [1, xlen) are never read; 32-bit byte offset from the
             // wave-uniform slot base (global_store saddr form)
             if (TB) tw.store((uint32_t *)(tb3 + ((uint32_t)(t - tb0) * RECB + (uint32_t)lane * (4u * NREC))));
-            // last column (rows 1 .. xlen-2) and last row (:481-484)
+            // last column, rows 1 .. xlen-2 (:481-484)
             uint32_t vl = cur[LAST ? K - 1 : 0];
             if (!LAST)
 #pragma unroll
                 for (int s = 1; s < K; ++s) vl = wv_bfi(lastm[s], cur[s], vl);
             uint32_t km = pk_neg_mask(pk_sub(vl, bestC));             // keep where vl < best (">=" takes)
-            if (CAREFUL) {
-                km |= pk_neg_mask(pk_sub(limp, ipk)) | pk_neg_mask(pk_sub(ipk, pk1(1)));
-                if (i >= 1 && (i == xl[0] - 1 || i == xl[1] - 1)) {
-                    for (int h = 0; h < 2; ++h) {
-                        if (!lact[h] || i != xl[h] - 1) continue;
-#pragma unroll
-                        for (int s = 0; s < K; ++s) {
-                            const int j = j0 + s, val = pk_score(cur[s], h);
-                            if (j >= 1 && j < yl[h] && val >= bestR[h]) { bestR[h] = val; bestRj[h] = j; }
-                        }
-                    }
-                }
+            const uint32_t tpk = (uint32_t)t * 0x10001u;              // wave-uniform: a scalar operand
+            if (HEAD || TAIL) {
+                const uint32_t ipk = pk_sub(tpk, glpk);               // this lane's row, both halves
+                if (TAIL) km |= pk_neg_mask(pk_sub(limp, ipk));
+                if (HEAD) km |= pk_neg_mask(pk_sub(ipk, pk1(1)));
             }
             bestC = wv_bfi(km, bestC, vl);
-            bestCi = wv_bfi(km, bestCi, ipk);
-            ipk = pk_add(ipk, 0x10001u);
+            bestCt = wv_bfi_u(km, bestCt, tpk);
             in0 = pre ? in1 : sN;
             outT = cur[K - 1]; outMS = mfS; outL = l0;
+        };
+        // The last row's best (:481-484), after the step that computed `cur`: each
+        // lane meets row xlen-1 of a half in one step (t = xlen-1 + gl), so only
+        // the TAIL steps call it, the wave skips the scan unless some lane is
+        // there, and that lane writes its result once (">=": its last column wins).
+        auto rowbest = [&](const int t, const uint32_t (&cur)[K]) WV_LAMBDA_INLINE {
+            const int i = t - gl;
+            const bool hit = i >= 1 && (i == xl[0] - 1 || i == xl[1] - 1);
+            if (!wv_any(hit)) return;
+            if (hit)
+                for (int h = 0; h < 2; ++h) {
+                    if (!lact[h] || i != xl[h] - 1) continue;
+                    int bR = INT_MIN, bRj = 0;
+#pragma unroll
+                    for (int s = 0; s < K; ++s) {
+                        const int j = j0 + s, val = pk_score(cur[s], h);
+                        if (j >= 1 && j < yl[h] && val >= bR) { bR = val; bRj = j; }
+                    }
+                    red[lane * 8 + 4 * h + 0] = bR; red[lane * 8 + 4 * h + 1] = bRj;
+                }
         };
         // Checkpoint m = the state before step 1 + m*CK, where the roles
         // are (cur, own) = (A, B), (in0, in1) = (I2, I1); register r of lane l
@@ -556,58 +591,52 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
         if (TWO) save(0);
         mark(0);
         // (cur, own) and (in0, in1) swap every step; every loop advances t by 2
-        // so the phase carries over
-        // (two-pass: steps inside the window write their traceback; t is odd
-        // here, so a pair is inside or outside the window as a whole)
-        auto inwin = [&](const int tt) { return TWO && tt >= tw0 && tt < tw1; };
+        // from 1, so the phase carries over and, in two-pass mode, a pair lies
+        // inside or outside the window [tw0, tw1) (both odd) as a whole
         int t = 1;
-        for (; t + 1 < tend && t <= G + 1; t += 2) {             // skewed start: lanes may be at row <= 1
-            ck(t);
-            if (inwin(t)) {
-                step(true, true, true, t, A, B, I2, I1);
-                step(true, true, true, t + 1, B, A, I1, I2);
-            } else {
-                step(true, true, TB1, t, A, B, I2, I1);
-                step(true, true, TB1, t + 1, B, A, I1, I2);
-            }
-        }
-        // every lane inside every record, row >= 2: before, inside and after
-        // the window as three loops (one loop with a branch spills)
-        auto fast = [&](const bool TBW, const int tlim) {
-            for (; t + 1 <= tlim; t += 2) {
+        auto pairs = [&](const bool HEAD, const bool TAIL, const bool TBW, const int tlim) WV_LAMBDA_INLINE {
+            // the counter and its bound are wave-uniform; said again here so that
+            // each loop is a scalar one (counter, checkpoint test and branch in SGPRs)
+            t = (int)wv_first((uint32_t)t);
+            const int tl = (int)wv_first((uint32_t)tlim);
+            for (; t + 1 <= tl; t += 2) {
                 ck(t);
-                step(false, false, TBW, t, A, B, I2, I1);
-                step(false, false, TBW, t + 1, B, A, I1, I2);
+                step(HEAD, TAIL, TBW, t, A, B, I2, I1);
+                if (TAIL) rowbest(t, A);
+                step(HEAD, TAIL, TBW, t + 1, B, A, I1, I2);
+                if (TAIL) rowbest(t + 1, B);
             }
         };
-        fast(TB1, min(xmin - 2, tw0 - 1));                       // pairs ending before tw0
-        if (TWO) {
-            fast(true, min(xmin - 2, tw1 - 1));                  // t >= tw0 here (both odd) or past the region
-            fast(false, xmin - 2);
-        }
-        for (; t + 1 < tend; t += 2) {
-            ck(t);
-            if (inwin(t)) {
-                step(false, true, true, t, A, B, I2, I1);
-                step(false, true, true, t + 1, B, A, I1, I2);
-            } else {
-                step(false, true, TB1, t, A, B, I2, I1);
-                step(false, true, TB1, t + 1, B, A, I1, I2);
+        // pairs up to step tlim: before, inside and after the window as three
+        // loops (one loop with a branch spills)
+        auto sweep = [&](const bool HEAD, const bool TAIL, const int tlim) WV_LAMBDA_INLINE {
+            pairs(HEAD, TAIL, TB1, min(tlim, tw0 - 1));          // pairs ending before tw0
+            if (TWO) {
+                pairs(HEAD, TAIL, true, min(tlim, tw1 - 1));     // t >= tw0 here (both odd) or past the region
+                pairs(HEAD, TAIL, false, tlim);
             }
-        }
+        };
+        // Each stretch pays for what can happen in it: the skewed start (lanes
+        // at rows <= 1) lasts to step G + 1, the end (lanes past row xlen-2 of
+        // the wave's shortest record) begins after step xmin - 2 and runs xmax -
+        // xmin + G + 1 steps; only records shorter than the skew see both at once.
+        const int tpair = tend - 1, thead = min(tpair, G + 2);
+        sweep(true, false, min(thead, xmin - 2));
+        sweep(true, true, thead);
+        sweep(false, false, xmin - 2);
+        sweep(false, true, tpair);
         if (t < tend) {
-            if (inwin(t)) step(true, true, true, t, A, B, I2, I1);
-            else          step(true, true, TB1, t, A, B, I2, I1);
+            if (TWO && t >= tw0 && t < tw1) step(true, true, true, t, A, B, I2, I1);
+            else                            step(true, true, TB1, t, A, B, I2, I1);
+            rowbest(t, A);
         }
         wv_mem_sync();                            // traceback / checkpoints written by all lanes
         mark(1);
 
         // best cell per half: row-major order, ">=" -> last visited wins
         for (int h = 0; h < 2; ++h) {
-            red[lane * 8 + 4 * h + 0] = bestR[h];
-            red[lane * 8 + 4 * h + 1] = bestRj[h];
             red[lane * 8 + 4 * h + 2] = ownC[h] ? pk_score(bestC, h) : INT_MIN;
-            red[lane * 8 + 4 * h + 3] = pk_half(bestCi, h);
+            red[lane * 8 + 4 * h + 3] = pk_half(bestCt, h) - gl;
         }
         wv_lds_sync();
         int bscore[2], bx[2], by[2];
@@ -669,6 +698,16 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
                     if (cov[h] && !lost && gl == 0 && in_group && P.win) wv_atomic_add(P.win, 1u);
                 }
                 wv_mem_sync();                    // walkers done before the second sweep overwrites the slot
+            }
+            // diagnostics (P.prof): waves of unpredicted candidates only that wrote
+            // the bottom window [12], and those it spared the second sweep [13]
+            if (P.prof) {
+                const bool pred = wv_any((valid[0] && prow[0] != NW16_NOROW) || (valid[1] && prow[1] != NW16_NOROW));
+                const bool left = wv_any(todo[0] || todo[1]);
+                if (!pred && lane == 0) {
+                    wv_atomic_add64(P.prof + 12, 1ull);
+                    if (!left) wv_atomic_add64(P.prof + 13, 1ull);
+                }
             }
             mark(4);
         }
@@ -781,7 +820,9 @@ __host__ static inline NwShape nw16_shape(uint32_t ymax, uint32_t xcap, int K = 
     if (s.G < 1) s.G = 1;
     s.GPW = 64 / s.G; s.nstr = 1;
     s.xcap = xcap < 2 ? 2 : (int)xcap;
-    s.xstride = (s.xcap + 15) & ~15;
+    // the record plus the G + 1 rows of padding the staging writes behind the
+    // wave's longest one (2000-base records at K = 19: 8 x 2016 of the 16 KB)
+    s.xstride = (s.xcap + s.G + 1 + 15) & ~15;
     while (s.GPW > 1 && (size_t)s.GPW * s.xstride > 16384) s.GPW--;
     s.steps = s.xcap + s.G;
     return s;

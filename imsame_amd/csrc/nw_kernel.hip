@@ -50,7 +50,7 @@ struct NwLaunch {
     int32_t  igap, egap;
     int32_t  G, GPW;             // lanes per group, groups per wave
     int32_t  xcap;               // max xlen of the launch
-    int32_t  xstride;            // LDS bytes per group for X (xcap rounded up)
+    int32_t  xstride;            // LDS bytes per group for X (xcap rounded up; nw16: + its padding rows)
     int32_t  steps;              // traceback steps per strip (xcap + G)
     uint32_t *tb;                // traceback scratch, one slot per resident wave
     uint64_t tb_wave_dw;         // dwords per slot

@@ -10,6 +10,9 @@
 #include <hip/hip_runtime.h>
 
 #define WV_DEVICE __device__ __forceinline__
+// a lambda whose constant flags select code: the call sites must fold them
+// (past its size threshold LLVM keeps a many-times-called lambda as a function)
+#define WV_LAMBDA_INLINE __attribute__((always_inline))
 
 // lane l receives lane l-1's value (lane 0 receives 0): DPP wave_shr:1 with
 // bound_ctrl zero fill (no v_mov to seed the destination's old value)
@@ -91,6 +94,12 @@ WV_DEVICE uint32_t wv_bfi(uint32_t m, uint32_t a, uint32_t b) {
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xca" : "=v"(r) : "v"(m), "v"(a), "v"(b));
     return r;
 }
+// wv_bfi with a wave-uniform b: read from a scalar register (one per VOP3), no copy to a VGPR
+WV_DEVICE uint32_t wv_bfi_u(uint32_t m, uint32_t a, uint32_t b) {
+    uint32_t r;
+    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xca" : "=v"(r) : "v"(m), "v"(a), "s"(b));
+    return r;
+}
 // byte permute of the 8 bytes {hi:lo}: selector byte k picks byte sel_k (0-3 of lo, 4-7 of hi)
 WV_DEVICE uint32_t wv_perm(uint32_t hi, uint32_t lo, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
 // the 32 bits of {hi:lo} from bit s up (s < 32): one v_alignbit_b32
@@ -113,6 +122,7 @@ WV_DEVICE uint32_t wv_shift_in(uint32_t w, bool c) {
 #include <atomic>
 
 #define WV_DEVICE inline
+#define WV_LAMBDA_INLINE
 #define __host__
 #define __device__
 #define __global__
@@ -215,6 +225,7 @@ inline uint32_t pk_neg_mask(uint32_t a) { return pk_map(a, 0, [](int x, int) { r
 inline uint32_t wv_shift_in(uint32_t w, bool c) { return (w << 1) | (c ? 1u : 0u); }
 inline uint32_t wv_and_or(uint32_t m, uint32_t c, uint32_t w) { return (m & c) | w; }
 inline uint32_t wv_bfi(uint32_t m, uint32_t a, uint32_t b) { return (m & a) | (~m & b); }
+inline uint32_t wv_bfi_u(uint32_t m, uint32_t a, uint32_t b) { return wv_bfi(m, a, b); }
 inline uint32_t wv_alignbit(uint32_t hi, uint32_t lo, uint32_t s) {
     return (uint32_t)((((uint64_t)hi << 32) | lo) >> (s & 31));
 }
