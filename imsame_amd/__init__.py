@@ -75,6 +75,7 @@ def lib():
         L.imsame_dev_open.argtypes = [C.c_int, C.POINTER(vp)]
         L.imsame_dev_close.argtypes = [vp]
         L.imsame_dev_index.argtypes = [vp, vp, u64, vp, u64, vp]
+        abi.bind_index_read(L)
         L.imsame_dev_set_query.argtypes = [vp, vp, u64, vp, u64]
         L.imsame_dev_set_query_range.argtypes = [vp, vp, u64, vp, u64, u64, u64]
         L.imsame_dev_set_query_range_async.argtypes = [vp, vp, u64, vp, u64, u64, u64]
@@ -206,6 +207,22 @@ class Device:
                                     len(db_starts), None if brk is None else brk.ctypes.data)
         if rc:
             raise ImsameError(rc, "imsame_dev_index")
+
+    def index_read(self):
+        """Diagnostic: the built index copied back (imsame_dev_index_read).
+        Returns (off uint64[4^12 + 1], ent ENT_DTYPE[n_ent] as stored, ent_abs:
+        True when x is the absolute position, False when record-relative)."""
+        n, ab = C.c_uint64(), C.c_int()
+        rc = lib().imsame_dev_index_read(self._h, None, None, 0, C.byref(n), C.byref(ab))
+        if rc and not (rc == abi.IMSAME_E_ARG and n.value > 0):
+            raise ImsameError(rc, "imsame_dev_index_read")
+        off = np.zeros(abi.NBUCKETS + 1, dtype=np.uint64)
+        ent = np.zeros(n.value, dtype=abi.ENT_DTYPE)
+        rc = lib().imsame_dev_index_read(self._h, off.ctypes.data, ent.ctypes.data if n.value else None, n.value,
+                                         C.byref(n), C.byref(ab))
+        if rc:
+            raise ImsameError(rc, "imsame_dev_index_read")
+        return off, ent, bool(ab.value)
 
     def set_query(self, q_seq, q_starts, read_from=None, read_to=None, wait=True):
         """Upload the query; with read_from/read_to only that shard's reads

@@ -65,6 +65,18 @@ PARITY_FIELDS = ("status", "db_seq", "score", "bx", "by", "length", "identities"
                  "igaps", "egaps", "head_x", "head_y", "ylen")
 
 
+NBUCKETS = 4 ** FIXED_K  # the index's direct-address buckets (one per 12-mer code)
+# one index entry as imsame_dev_index_read returns it: {x, record}
+ENT_DTYPE = np.dtype([("x", "<u4"), ("record", "<u4")])
+assert ENT_DTYPE.itemsize == 8
+
+
+def bind_index_read(L):
+    """argtypes of imsame_dev_index_read (include/imsame_dev.h)."""
+    L.imsame_dev_index_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_int)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("n_reads", C.c_uint64), ("n_accepted", C.c_uint64), ("n_nw", C.c_uint64),

@@ -904,6 +904,23 @@ extern "C" int imsame_dev_index(imsame_ctx *c, const uint8_t *db_seq, uint64_t d
     return IMSAME_OK;
 }
 
+// the built CSR as it lies in HBM (a diagnostic: the tests compare it with a
+// plain host reference of IMSAME.c:229-281)
+extern "C" int imsame_dev_index_read(imsame_ctx *c, uint64_t *off, uint32_t *ent, uint64_t ent_cap, uint64_t *n_ent,
+                                     int *ent_abs) {
+    if (!c) return IMSAME_E_ARG;
+    if (!c->have_index) return IMSAME_E_STATE;
+    if (n_ent) *n_ent = c->n_ent;
+    if (ent_abs) *ent_abs = c->ent_abs ? 1 : 0;
+    if (ent_cap < c->n_ent || (c->n_ent && !ent)) return IMSAME_E_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    if (off) HIPCHK(hipMemcpyAsync(off, c->off.p, ((uint64_t)NBUCKETS + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (c->n_ent) HIPCHK(hipMemcpyAsync(ent, c->ent.p, c->n_ent * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return IMSAME_OK;
+}
+
 // parts of an asynchronous query upload (each a few tens of MB at C2)
 #define Q_PARTS 8
 

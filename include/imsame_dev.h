@@ -204,6 +204,20 @@ const char *imsame_strerror(int code);
 int imsame_dev_index(imsame_ctx *ctx, const uint8_t *db_seq, uint64_t db_len,
                      const uint64_t *db_start, uint64_t n_db, const uint8_t *db_brk);
 
+/* Diagnostic (the tests' view of the index; no other caller): copy the index
+ * imsame_dev_index built back to the host.
+ *   off     : 4^12 + 1 bucket offsets (bucket b = entries off[b] .. off[b+1]),
+ *             may be NULL
+ *   ent     : ent_cap pairs of u32, {x, record} per entry as stored: x is the
+ *             reference's pos (the k-mer's last base + 1, IMSAME.c:247) in the
+ *             absolute form, pos - start[record] in the relative form
+ *   n_ent   : receives the entry count, ent_abs 1 for the absolute form
+ * IMSAME_E_STATE when no index is loaded; IMSAME_E_ARG, with *n_ent set, when
+ * ent_cap is below the entry count (nothing is copied).  The index is neither
+ * rebuilt nor changed. */
+int imsame_dev_index_read(imsame_ctx *ctx, uint64_t *off, uint32_t *ent, uint64_t ent_cap,
+                          uint64_t *n_ent, int *ent_abs);
+
 /* Upload the query (IMSAME.c:320-371 output): ACGT-filtered concatenation
  * and n_q read starts. */
 int imsame_dev_set_query(imsame_ctx *ctx, const uint8_t *q_seq, uint64_t q_len,

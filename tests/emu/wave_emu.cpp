@@ -331,6 +331,22 @@ static void build_csr(const uint8_t *db, uint64_t L, const uint64_t *dbs, uint64
     }
 }
 
+// build_csr for the tests (every emulated pipeline rests on it): off holds
+// NBUCKETS + 1 offsets, ent up to ent_cap {x, record} pairs; returns the entry
+// count (nothing is copied to ent when it exceeds ent_cap)
+extern "C" uint64_t emu_build_csr(const uint8_t *db, uint64_t db_len, const uint64_t *db_start, uint64_t n_db,
+                                  const uint8_t *db_brk, int abs, uint64_t *off_out, uint32_t *ent_out,
+                                  uint64_t ent_cap) {
+    std::vector<uint64_t> dbs(db_start, db_start + n_db), off;
+    dbs.push_back(db_len);
+    std::vector<uint2> ent;
+    build_csr(db, db_len, dbs.data(), n_db, db_brk, off, ent, abs != 0);
+    const uint64_t n = off[NBUCKETS];
+    if (off_out) memcpy(off_out, off.data(), ((size_t)NBUCKETS + 1) * 8);
+    if (ent_out && n && n <= ent_cap) memcpy(ent_out, ent.data(), n * 8);
+    return n;
+}
+
 extern "C" int emu_align(const uint8_t *db, uint64_t db_len, const uint64_t *db_start, uint64_t n_db,
                          const uint8_t *db_brk, const uint8_t *q, uint64_t q_len, const uint64_t *q_start,
                          uint64_t n_q, uint64_t read_from, uint64_t read_to, uint64_t T, const imsame_params *p,

@@ -10,7 +10,7 @@ import subprocess
 
 import numpy as np
 
-from imsame_amd.abi import Params, Stats, RESULT_DTYPE
+from imsame_amd.abi import Params, Stats, RESULT_DTYPE, ENT_DTYPE, NBUCKETS
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 EMU_DIR = os.path.join(HERE, "emu")
@@ -37,6 +37,24 @@ class Emu:
                                   C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(Params),
                                   C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                   C.POINTER(Stats)]
+
+        lib.emu_build_csr.restype = C.c_uint64
+        lib.emu_build_csr.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_uint64]
+
+    def build_csr(self, db, db_start, db_brk=None, ent_abs=True):
+        """The host index every emulated pipeline runs on (wave_emu.cpp:
+        build_csr): (off uint64[4^12 + 1], ent ENT_DTYPE[n_ent])."""
+        db = np.ascontiguousarray(db, dtype=np.uint8)
+        dbs = np.ascontiguousarray(db_start, dtype=np.uint64)
+        brk = None if db_brk is None else np.ascontiguousarray(db_brk, dtype=np.uint8)
+        off = np.zeros(NBUCKETS + 1, dtype=np.uint64)
+        ent = np.zeros(max(len(db), 1), dtype=ENT_DTYPE)          # at most one entry per base
+        n = self.lib.emu_build_csr(db.ctypes.data, len(db), dbs.ctypes.data, len(dbs),
+                                   None if brk is None else brk.ctypes.data, 1 if ent_abs else 0,
+                                   off.ctypes.data, ent.ctypes.data, len(ent))
+        assert n <= len(ent)
+        return off, ent[:n]
 
     def nw_pairs(self, X, Y, params, paths_cap=0):
         xs = np.frombuffer(b"".join(X), dtype=np.uint8).copy()

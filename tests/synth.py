@@ -243,3 +243,247 @@ NW16_LIMIT_CASES = [
     ("k10_300x160", {}, 10, 300, 160, [(-3, -5957), (-8, -3327)]),
     ("k10_3000x31", {}, 10, 3000, 31, [(-1, -4909), (-2, -1803)]),
 ]
+
+
+# ---------------------------------------------------------------------------
+# the database index, restated (tests/test_index_repeats.py)
+# ---------------------------------------------------------------------------
+INDEX_K = 12
+INDEX_BUCKETS = 4 ** INDEX_K
+
+
+def kmer_code(word):
+    """code of a 12-mer (bytes / uint8 array): 2 bits per base, A0 C1 G2 T3,
+    the first base most significant"""
+    c = 0
+    for b in np.searchsorted(ACGT, np.frombuffer(bytes(word), dtype=np.uint8)).tolist():
+        c = c * 4 + b
+    return c
+
+
+def index_reference(seq, starts, brk=None, relative=False):
+    """The 12-mer index by the rule the reference follows (IMSAME.c:229-281):
+    for every base p >= 11 the 12-mer ending at p is indexed unless a reset --
+    a record start, or a set bit of brk (LSB-first) -- lies before one of the
+    bases p-10 .. p.  Its record is the last one whose start is <= p, its
+    stored position p + 1 (relative: minus that record's start).  Buckets
+    ascend by code; inside a bucket positions descend (the reference's LIFO
+    chain).  Returns (off uint64[4^12 + 1], ent {x, record} uint32 pairs)."""
+    from imsame_amd.abi import ENT_DTYPE
+    seq = np.asarray(seq, dtype=np.uint8)
+    st = np.asarray(starts, dtype=np.int64)
+    L, K = len(seq), INDEX_K
+    off = np.zeros(INDEX_BUCKETS + 1, dtype=np.uint64)
+    if L < K:
+        return off, np.zeros(0, dtype=ENT_DTYPE)
+    reset = np.zeros(L, dtype=bool)
+    reset[st[st < L]] = True
+    if brk is not None:
+        bits = np.unpackbits(np.asarray(brk, dtype=np.uint8), bitorder="little")[:L]
+        reset[:len(bits)] |= bits.astype(bool)
+    nres = np.concatenate([[0], np.cumsum(reset)])                 # resets among bases [0, i)
+    p = np.arange(K - 1, L, dtype=np.int64)
+    two = np.searchsorted(ACGT, seq).astype(np.int64)
+    code = np.zeros(L - K + 1, dtype=np.int64)
+    for t in range(K):
+        code = code * 4 + two[t:t + L - K + 1]                     # the 12-mer that starts at p - 11
+    keep = nres[p + 1] == nres[p - (K - 2)]                        # no reset at p-10 .. p
+    p, code = p[keep], code[keep]
+    rec = np.searchsorted(st, p, side="right") - 1
+    order = np.lexsort((-p, code))
+    p, rec = p[order], rec[order]
+    ent = np.zeros(len(p), dtype=ENT_DTYPE)
+    ent["x"] = p + 1 - (st[rec] if relative else 0)
+    ent["record"] = rec
+    off[1:] = np.cumsum(np.bincount(code, minlength=INDEX_BUCKETS))
+    return off, ent
+
+
+def _rand(rng, n):
+    return ACGT[rng.integers(0, 4, n)]
+
+
+def _substitute(rng, y, rate):
+    y = y.copy()
+    m = rng.random(len(y)) < rate
+    y[m] = ACGT[(np.searchsorted(ACGT, y[m]) + rng.integers(1, 4, int(m.sum()))) % 4]
+    return y
+
+
+# copies of the planted 12-mers: both sides of the index sort's limits (32
+# entries: insertion sort / bitonic; 4096: LDS / global scratch; padded sizes
+# 4096 in LDS, 8192 and 16384 in scratch)
+PLANTED_COUNTS = (1, 2, 31, 32, 33, 64, 65, 4095, 4096, 4097, 8192, 8193)
+PLANTED_BRK = 48          # one more planted 12-mer: resets inside PLANTED_BRK_CUT of its copies
+PLANTED_BRK_CUT = 10
+COPY_LEN, COPY_N = 100, 5000
+BRK_PHASES = (0, 1, 20, 21, 22, 30, 31)
+
+
+def make_repetitive_db(seed=2024):
+    """One database of ~1.5 Mbp for the index tests: planted 12-mers, repeats,
+    record edges and a reset bitmap.  Returns a dict:
+      seq, starts, brk        the database (brk: the optional reset bitmap)
+      planted                 {copies: code} of the 12-mers planted `copies` times
+      brk_code                the 12-mer planted PLANTED_BRK times, PLANTED_BRK_CUT of them cut by brk
+      copy_unit, copy_first   the 100-base record repeated COPY_N times, and its first record
+      polya, dinuc, tiled     record numbers of the first poly-A, the dinucleotide and the tiled record
+      unique                  (first record, record count, record length) of plain random records
+      words                   {copies: 12-mer bytes}
+    The generator asserts, from index_reference alone, that the buckets hold
+    exactly these sizes with and without brk."""
+    for attempt in range(64):
+        d = _repetitive_db(np.random.default_rng([seed, attempt]))
+        if d is not None:
+            return d
+    raise AssertionError("no layout with exact planted counts")
+
+
+def _repetitive_db(rng):
+    counts = list(PLANTED_COUNTS) + [PLANTED_BRK]
+    # distinct 12-mers; the huge buckets' codes ascend with their size, so the
+    # build meets them in growing order (its scratch area is regrown)
+    codes = np.sort(rng.choice(np.arange(1 << 10, INDEX_BUCKETS - (1 << 10)), len(counts), replace=False))
+    words = {}
+    for n, c in zip(sorted(counts), codes.tolist()):
+        words[n] = ACGT[[(c >> (2 * (INDEX_K - 1 - t))) & 3 for t in range(INDEX_K)]]
+    wid = rng.permutation(np.repeat(np.arange(len(counts)), counts))
+    wtab = np.stack([words[n] for n in counts])
+    units = np.empty((len(wid), 32), dtype=np.uint8)               # 20 random bases, then the 12-mer
+    units[:, :20] = _rand(rng, (len(wid), 20))
+    units[:, 20:] = wtab[wid]
+    parts, lens = [], []                                           # records, in order
+
+    def rec(a):
+        parts.append(np.asarray(a, dtype=np.uint8))
+        lens.append(len(a))
+
+    # planted zone: records of ragged lengths 13 .. 3000: 0 .. 31 random bases
+    # (the copies' positions take every phase of a 32-bit bitmap word), then
+    # whole units
+    u, word_pos = 0, [[] for _ in counts]
+    base = 0
+    while u < len(wid):
+        k = int(min(len(wid) - u, rng.choice([0, 1, 2, 5, 20, 60, 92], p=[.1, .2, .2, .2, .15, .1, .05])))
+        pad = int(rng.integers(13, 32)) if k == 0 else int(rng.integers(0, 32))
+        rec(np.concatenate([_rand(rng, pad), units[u:u + k].reshape(-1)]))
+        for j in range(k):
+            word_pos[wid[u + j]].append(base + pad + 32 * j + 20)  # first base of the copy
+        base += lens[-1]
+        u += k
+    info = {}
+    # repeats
+    info["polya"] = len(lens)
+    for _ in range(3):
+        rec(np.full(2000, ord("A"), np.uint8))
+    info["dinuc"] = len(lens)
+    rec(np.tile(np.frombuffer(b"AC", np.uint8), 750))
+    info["tiled"] = len(lens)
+    rec(np.tile(_rand(rng, 7), 200))
+    unit = _rand(rng, COPY_LEN)
+    info["copy_unit"], info["copy_first"] = unit, len(lens)
+    for _ in range(COPY_N):
+        rec(unit)
+    # plain random records (reads' unique origins; resets at every bitmap phase)
+    info["unique"] = (len(lens), 60, 700)
+    uniq_base = sum(lens)
+    for _ in range(60):
+        rec(_rand(rng, 700))
+    # record edges: 12, 0, 0, 1, 11, 13, 0, 12 bases, a k-mer across two
+    # records at every start, then 40 bases and an empty last record
+    for n in (12, 0, 0, 1, 11, 13, 0, 12, 40, 0):
+        rec(_rand(rng, n))
+    seq = np.concatenate(parts)
+    starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64)
+    L = len(seq)
+    assert int(starts[-1]) == L and lens[-2] == 40
+    # the reset bitmap
+    bit = np.zeros(8 * ((L + 7) // 8), dtype=np.uint8)
+    words32 = rng.choice(np.arange(uniq_base // 32 + 1, (uniq_base + 60 * 700) // 32), 700, replace=False)
+    bit[words32 * 32 + rng.choice(BRK_PHASES, len(words32))] = 1
+    for w, n in enumerate(counts):                 # right before and after planted copies: none is lost
+        pos = np.array(word_pos[w])
+        if n == PLANTED_BRK:                       # ... and inside: those copies are not indexed
+            for k, s in enumerate(pos[:PLANTED_BRK_CUT]):
+                bit[s + (1, 5, 11)[k % 3]] = 1
+            continue
+        some = pos[rng.random(len(pos)) < 0.1] if n > 2 else pos
+        bit[some[0::3]] = 1                        # the copy's first base: the reset before it
+        bit[some[1::3] + INDEX_K] = 1              # the base after the copy
+        bit[some[2::3] - 1] = 1
+    bit[0] = 1
+    bit[[L - 12, L - 7, L - 1]] = 1
+    brk = np.packbits(bit, bitorder="little")
+    # the fixture's proof: exact bucket sizes by the plain reference
+    sizes = {}
+    for b in (None, brk):
+        off, _ = index_reference(seq, starts, b)
+        size = np.diff(off.astype(np.int64))
+        for n in counts:
+            want = n - (PLANTED_BRK_CUT if (n == PLANTED_BRK and b is not None) else 0)
+            if size[kmer_code(words[n])] != want:
+                return None                        # a 12-mer arose by chance elsewhere: draw again
+        if b is None:
+            assert size[0] == 3 * (2000 - 11)
+            ucodes = [kmer_code(unit[t:t + INDEX_K]) for t in range(COPY_LEN - INDEX_K + 1)]
+            if len(set(ucodes)) != len(ucodes) or not (size[ucodes] == COPY_N).all():
+                return None
+        sizes[b is not None] = size
+    info.update(seq=seq, starts=starts, brk=brk, words={n: words[n].tobytes() for n in counts},
+                planted={n: kmer_code(words[n]) for n in PLANTED_COUNTS}, brk_code=kmer_code(words[PLANTED_BRK]))
+    return info
+
+
+def make_families_db(seed=515, members=(450, 450, 20), length=300, total=300_000, sub=0.10):
+    """~300 kbp of 300-base records: one family per entry of `members` (the
+    family sequence with each member's own substitutions) scattered among
+    random records.  Returns (seq, starts, family sequences, member record
+    numbers per family, ascending)."""
+    rng = np.random.default_rng(seed)
+    n_rec = total // length
+    perm = rng.permutation(n_rec)
+    recs = _rand(rng, (n_rec, length))
+    fam, where, u = [], [], 0
+    for m in members:
+        fam.append(_rand(rng, length))
+        where.append(np.sort(perm[u:u + m]))
+        u += m
+        for r in where[-1]:
+            recs[r] = _substitute(rng, fam[-1], sub)
+    return recs.reshape(-1), np.arange(0, n_rec * length, length, dtype=np.uint64), fam, where
+
+
+def make_resume_db(seed=717, copies=40):
+    """A scan that resumes inside a bucket (its cursor's hit rank > 0) while
+    the windows next to it hold the record to accept.  A 100-base unit is in
+    the database `copies` times back to back; below them lie 70-base records cut
+    from the unit's tiling across a junction (phases 89 .. 99), which own the
+    12-mers that span two copies -- no copy is indexed with those.  A read of
+    the tiling that starts at such a phase meets the 70-base record alone in
+    its first windows: it passes the e-value, covers 70 / 150 of the read and
+    is rejected, and the scan resumes after that hit.  Seven or fewer windows
+    on, the buckets hold every copy, the highest-positioned first: any copy
+    would be accepted with the same NW row, so db_seq tells which one the scan
+    took first.  Returns (seq, starts, reads, first copy record, copies); reads
+    0, 2, .. 10 start at a junction phase, 1, 3, .. 11 three bases before one,
+    the last two are random."""
+    rng = np.random.default_rng(seed)
+    unit = _rand(rng, 100)
+    tiling = np.tile(unit, 4)
+    recs = [_rand(rng, 300) for _ in range(100)]
+    phases = (89, 91, 93, 95, 97, 99)
+    recs += [tiling[f:f + 70] for f in phases]
+    recs += [tiling[93:93 + 70]] * 8               # nine of phase 93: more than a round's 8 candidates,
+                                                   # so a round ends inside their bucket at rank 8
+    first = len(recs)
+    recs += [unit] * copies
+    recs += [_rand(rng, 300) for _ in range(20)]
+    lens = [len(r) for r in recs]
+    reads = []
+    for f in phases:
+        for back in (0, 3):                        # the junction record's first own window: the read's first, or its fourth
+            y = tiling[f - back:f - back + 150].copy()
+            y[90:] = _substitute(rng, y[90:], 0.02)
+            reads.append(y)
+    reads += [_rand(rng, 150) for _ in range(2)]
+    return (np.concatenate(recs), np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64), reads, first, copies)
