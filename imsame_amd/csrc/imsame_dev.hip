@@ -380,6 +380,10 @@ struct imsame_ctx {
     // every lane draws from the chip's residency in one arena (np_prepare)
     DBuf np_tb, np_ck;
     imsame_ctx *np_owner = nullptr;   // lanes: the context whose arena they use
+    // the slot layout of the running call (np_strides): its short class holds
+    // mid reads.  Set by align_impl before the lanes start; every launch of
+    // the call, on any lane, numbers the arena's slots by it.
+    bool np_mid = false;
     uint64_t paths_cap_dev = 0, paths_n = 0;
     double paths_hint = 0;     // path entries per read of the last call
     std::vector<uint32_t> paths_host;
@@ -1113,6 +1117,7 @@ static void timeline_print(const std::vector<imsame_ctx *> &L) {
 }
 
 struct NwPlan { int G, GPW, xcap, xstride, steps, nstr, k; bool pk, last4, two, lng, lp, np; size_t lds; unsigned blocks, max_blocks;
+                bool mid;              // pk: the 10-column form of reads of 161 .. NW16_YMAX bases (nw16_mid_kernel)
                 uint32_t slot_words;   // np: bitmap words per XCD partition (arena slots = 8 x 32 x slot_words)
                 uint64_t tb_dw, ck_dw, bnd_dw; int band_w; };
 
@@ -1135,20 +1140,39 @@ static bool nwp_enabled() {
 // path longer than that (rare: C2 paths span <= 209 rows) makes its wave redo
 // the sweep over 4 bands, then from row 1.  IMSAME_NW_BAND overrides (tests
 // use tiny bands to drive the redo path).
-static int nw16_band_rows() {
+// Mid launches (ymax > 160): ymax + 40 rows.  An accepted read's path spans
+// about its length in rows, so under 200 rows every 250- or 300-base
+// candidate that its wave's predicted window did not cover redid its sweep
+// at 4 bands (23k / 29k redo waves of 400k reads; at 200 bases 5.6k).  Per
+// step of 400k reads at bands 200 / 280 / 340 / 400 (profiles/nw16_mid/
+// bench.md): 200 bases 69.6 / 67.0 / 68.1 / 68.8 ms, 250 bases 115.8 / 108.8
+// / 109.6 / 111.2, 300 bases 133.9 / 136.1 / 129.0 / 131.1 -- the least a
+// little above the read length, wider bands only add steps.
+static int nw16_band_rows(uint32_t ymax) {
     const char *e = getenv("IMSAME_NW_BAND");
-    return e ? std::max(0, atoi(e)) : 200;
+    return e ? std::max(0, atoi(e)) : ymax > NW_W / 2 ? (int)ymax + 40 : 200;
 }
 
 
 // Slot strides of the non-persistent arena: the largest packed shape of a
 // record cap (reads <= NW_W/2, either column form), so the launches of every
 // lane of a call -- whose read lengths differ -- share one layout.
-static void np_strides(uint32_t xcap, uint64_t *tb_dw, uint64_t *ck_dw) {
+// mid: the call's short class holds reads of 161 .. NW16_YMAX bases
+// (imsame_ctx::np_mid: the layout is the call's), so the mid shape counts
+// too.  A call without them sizes exactly what it did before.  (From a record
+// cap of 17 rows on the mid shape adds nothing: per step it writes 3 traceback
+// dwords per lane over xcap + 32 steps against the 19-column form's 6 over
+// xcap + 8, and 45 checkpoint dwords every 32 steps against 81 every 48.)
+static void np_strides(uint32_t xcap, bool mid, uint64_t *tb_dw, uint64_t *ck_dw) {
     const NwShape a = nw16_shape(NW_W / 2, xcap, NW16_K), b = nw16_shape(NW_W / 2, xcap, NW16_K5),
                   d = nw16_shape(NW16_K19_YLEN, xcap, NW16_K19), e = nw16_shape(NW16_K3_YMAX, xcap, NW16_K3);
     *tb_dw = std::max(std::max(nw16_tb_words(a), nw16_tb_words(b)), std::max(nw16_tb_words(d), nw16_tb_words(e)));
     *ck_dw = std::max(std::max(nw16_ck_words(a), nw16_ck_words(b)), std::max(nw16_ck_words(d), nw16_ck_words(e)));
+    if (mid) {
+        const NwShape m = nw16_shape(NW16_YMAX, xcap, NW16_K);
+        *tb_dw = std::max(*tb_dw, nw16_tb_words(m));
+        *ck_dw = std::max(*ck_dw, nw16_ck_words(m));
+    }
 }
 
 // Blocks per CU the XCD partitions of a context's slot bitmap hold: the
@@ -1172,6 +1196,8 @@ static int nw16_np_part_cu(imsame_ctx *c) {
     q((const void *)nw16_kernel<NW16_K19, true, false, NW16_K19_OFF>);
     q((const void *)nw16_kernel<NW16_K3, false, true>); q((const void *)nw16_kernel<NW16_K3, true, true>);
     q((const void *)nw16_kernel<NW16_K3, false, false>); q((const void *)nw16_kernel<NW16_K3, true, false>);
+    q((const void *)nw16_mid_kernel<false, true>);  q((const void *)nw16_mid_kernel<true, true>);
+    q((const void *)nw16_mid_kernel<false, false>); q((const void *)nw16_mid_kernel<true, false>);
     c->np_part_cu = ok ? m : 0;
     return c->np_part_cu;
 }
@@ -1270,18 +1296,24 @@ static int plan_nw(imsame_ctx *c, uint32_t ymax, uint32_t xcap, uint32_t ncand, 
     // candidates again.  Results are identical (tests run every kernel).
     const char *se = getenv("IMSAME_NW_SMALL");
     const uint32_t small = (p->flags & IMSAME_FLAG_NW16) || !rounds ? 0u : se ? (uint32_t)atoi(se) : 0u;
+    // Mid launches (160 < ymax <= NW16_YMAX): the packed kernel's mid form where
+    // the range proof admits the launch (IMSAME_NW_MID=0: the long kernels, as
+    // before).  Always 10 columns -- the 5- and 3-column forms cannot hold CK +
+    // G <= 64 there -- so nw16_k's fill rule and IMSAME_NW_K do not apply.
+    const bool midy = ymax > NW_W / 2;
     pl->pk = !(p->flags & IMSAME_FLAG_NW32) && ncand >= small && nw16_fits(p->igap, p->egap, xcap, ymax);
+    pl->mid = pl->pk && midy;
     pl->last4 = pl->pk && ylen_mult;
     const char *op = getenv("IMSAME_NW_ONEPASS");
     pl->two = pl->pk && !(p->flags & IMSAME_FLAG_NW16_ONEPASS) && !(op && atoi(op));
-    pl->band_w = nw16_band_rows();
+    pl->band_w = nw16_band_rows(ymax);
     pl->lng = !pl->pk && !(p->flags & IMSAME_FLAG_NW32) && nwl_enabled() && nwl_fits(p->igap, p->egap, ymax);
     if (pl->lng) {                  // steps of a pass-2 band (IMSAME_NWL_BAND: tests use small ones)
         const char *nb = getenv("IMSAME_NWL_BAND");
         pl->band_w = nb ? std::max(1, std::min(NWL_BAND, atoi(nb))) : NWL_BAND_DEF;
     }
     pl->lp = pl->lng && nwp_enabled() && nwp_fits(p->igap, p->egap, xcap, ymax);
-    pl->k = pl->pk ? nw16_k(c, ncand, rounds) : 0;
+    pl->k = pl->mid ? NW16_K : pl->pk ? nw16_k(c, ncand, rounds) : 0;
     if (pl->k == NW16_K3) {
         // the latency form: reads <= NW16_K3_YMAX (CK + G <= 64, nw16_fits) whose
         // values fit its wider column count; LAST when the launch's one read
@@ -1306,6 +1338,10 @@ static int plan_nw(imsame_ctx *c, uint32_t ymax, uint32_t xcap, uint32_t ncand, 
     const bool k5 = pl->k == NW16_K5, k19 = pl->k == NW16_K19, k3 = pl->k == NW16_K3;
     hipError_t oe = pl->lp ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nwp_kernel, wpb * 64, pl->lds)
                   : pl->lng ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nwl_kernel, wpb * 64, pl->lds)
+                  : pl->mid ? (pl->two ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nw16_mid_kernel<false, true>,
+                                                                                  wpb * 64, pl->lds)
+                                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nw16_mid_kernel<false, false>,
+                                                                                  wpb * 64, pl->lds))
                   : k3 ? (pl->two ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nw16_kernel<NW16_K3, false, true>,
                                                                              wpb * 64, pl->lds)
                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nw16_kernel<NW16_K3, false, false>,
@@ -1336,16 +1372,18 @@ static int plan_nw(imsame_ctx *c, uint32_t ymax, uint32_t xcap, uint32_t ncand, 
         // forms, on one arena and bitmap.  Strides of the larger form;
         // partitions for the larger residency without LDS (LDS only lowers it).
         part_cu = nw16_np_part_cu(c);
+        const imsame_ctx *ao = c->np_owner ? c->np_owner : c;
         uint64_t tb_dw = 0, ck_dw = 0;
-        np_strides(xcap, &tb_dw, &ck_dw);
+        np_strides(xcap, ao->np_mid, &tb_dw, &ck_dw);       // the call's layout (align_impl)
         const uint32_t words = (uint32_t)((((uint64_t)c->ncu / 8) * part_cu * wpb + 31) / 32);
         const uint64_t ns = (uint64_t)8 * 32 * words;
         // the arena np_prepare actually holds (it skips the allocation when
         // free HBM is short, e.g. after a long-read call grew c->tb): a plan
         // is non-persistent only if its slots exist, so two launches planned
         // np (round 1b) never fall back to one persistent arena together
-        const imsame_ctx *ao = c->np_owner ? c->np_owner : c;
-        if (part_cu < per_cu || ao->np_tb.cap < ns * tb_dw * 4 || ao->np_ck.cap < ns * ck_dw * 4 ||
+        // (a mid launch of a call whose layout leaves the mid shape out stays
+        // persistent: its slots may be larger than the layout's)
+        if (part_cu < per_cu || (pl->mid && !ao->np_mid) || ao->np_tb.cap < ns * tb_dw * 4 || ao->np_ck.cap < ns * ck_dw * 4 ||
             ao->slotbits.cap < (uint64_t)8 * words * 4)
             pl->np = false;
         else { pl->tb_dw = tb_dw; pl->ck_dw = ck_dw; }
@@ -1422,7 +1460,7 @@ static int np_prepare(imsame_ctx *o, uint32_t xcap) {
     const uint32_t words = (uint32_t)((((uint64_t)o->ncu / 8) * nw16_np_part_cu(o) * 4 + 31) / 32);
     const uint64_t ns = (uint64_t)8 * 32 * words, nbits = (uint64_t)8 * words * 4;
     uint64_t tb_dw = 0, ck_dw = 0;
-    np_strides(xcap < 2 ? 2 : xcap, &tb_dw, &ck_dw);
+    np_strides(xcap < 2 ? 2 : xcap, o->np_mid, &tb_dw, &ck_dw);
     const uint64_t need_tb = ns * tb_dw * 4, need_ck = ns * ck_dw * 4;
     if (o->np_tb.cap >= need_tb && o->np_ck.cap >= need_ck && o->slotbits.cap >= nbits) return 0;
     size_t fr = 0, tot = 0;
@@ -1560,6 +1598,10 @@ static int launch_nw(imsame_ctx *c, NwPlan &pl, const uint32_t *cread, const uin
     }
     if (pl.lp)                         nwp_kernel<<<pl.blocks, 256, pl.lds, s>>>(P);
     else if (pl.lng)                   nwl_kernel<<<pl.blocks, 256, pl.lds, s>>>(P);
+    else if (pl.mid && pl.two && pl.last4) nw16_mid_kernel<true, true><<<pl.blocks, 256, pl.lds, s>>>(P);
+    else if (pl.mid && pl.two)         nw16_mid_kernel<false, true><<<pl.blocks, 256, pl.lds, s>>>(P);
+    else if (pl.mid && pl.last4)       nw16_mid_kernel<true, false><<<pl.blocks, 256, pl.lds, s>>>(P);
+    else if (pl.mid)                   nw16_mid_kernel<false, false><<<pl.blocks, 256, pl.lds, s>>>(P);
     else if (pl.k == NW16_K19 && pl.two) nw16_kernel<NW16_K19, true, true, NW16_K19_OFF><<<pl.blocks, 256, pl.lds, s>>>(P);
     else if (pl.k == NW16_K19)         nw16_kernel<NW16_K19, true, false, NW16_K19_OFF><<<pl.blocks, 256, pl.lds, s>>>(P);
     else if (pl.k == NW16_K3 && pl.two && pl.last4) nw16_kernel<NW16_K3, true, true><<<pl.blocks, 256, pl.lds, s>>>(P);
@@ -1726,7 +1768,10 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
     if (n == 0) { if (stats) *stats = st; return IMSAME_OK; }
     // the rounds' policy (round_policy.h, shared with the CPU emulator):
     // list capacity, speculation, budgets, scan group sizes, round 1b
-    const uint32_t short_y = std::min<uint32_t>(ycap, NW_W / 2);
+    // the short class: reads the packed kernel takes (nw_short_max: up to
+    // NW16_YMAX where the mid form can run this call's class, else NW_W/2);
+    // round 1b, split rounds, pipelines, predicted rows and rewalk_lost follow it
+    const uint32_t short_y = std::min<uint32_t>(ycap, nw_short_max(p, xcap, ycap));
     const RoundPolicy RP = RoundPolicy::make(n, ycap, short_y, c->nlanes);
     const uint64_t ccap = RP.ccap;
     if (c->res.ensure((uint64_t)n * 64) || c->cur_p.ensure((uint64_t)n * 8) || c->cur_h.ensure((uint64_t)n * 4) ||
@@ -2503,6 +2548,24 @@ extern "C" int imsame_dev_align_parts(imsame_ctx *c, uint64_t read_from, uint64_
     return align_impl(c, read_from, read_to, n_threads_semantic, p, res, nullptr, 0, &used, stats, fn, user);
 }
 
+// Lanes a call of mid reads may take: each may hold a persistent arena of the
+// mid shape at full residency (ncu x 3 blocks x 4 waves slots, align_impl's
+// arithmetic), beside 8 GB of headroom -- the budget rule of plan_nw.
+static int mid_lane_cap(const imsame_ctx *c, uint32_t xcap) {
+    const NwShape m = nw16_shape(NW16_YMAX, xcap, NW16_K);
+    const uint64_t per_lane = (uint64_t)c->ncu * 3 * 4 * (nw16_tb_words(m) + nw16_ck_words(m)) * 4;
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) != hipSuccess) return 1;
+    uint64_t held = c->tb.cap + c->bnd.cap + c->ck.cap;            // (plan_nw's `held`, over the lanes)
+    for (const imsame_ctx *l : c->subs) held += l->tb.cap + l->bnd.cap + l->ck.cap;
+    uint64_t avail = fr + held;
+    const uint64_t headroom = 8ull << 30;
+    // test hook: behave as if this many bytes were free or held (IMSAME_DEBUG_NP_SKIP's kind)
+    if (const char *fh = getenv("IMSAME_DEBUG_MID_HBM")) avail = strtoull(fh, nullptr, 10);
+    if (avail <= headroom) return 1;
+    return (int)std::max<uint64_t>(1, std::min<uint64_t>(LANES_MAX, (avail - headroom) / std::max<uint64_t>(per_lane, 1)));
+}
+
 static int align_impl(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64_t n_threads_semantic,
                       const imsame_params *p, imsame_read_result *res, uint32_t *paths, uint64_t paths_cap,
                       uint64_t *paths_used, imsame_stats *stats, imsame_part_fn fn, void *user) {
@@ -2519,8 +2582,13 @@ static int align_impl(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint6
     const uint64_t n = read_to - read_from;
     uint64_t ymax = 0;
     ymax = range_ymax(c, read_from, read_to);
-    if (!c->is_sub && ymax <= (uint64_t)NW_W / 2 && n) {   // the lanes' shared NW arena, before they start
-        const int rp = np_prepare(c, (uint32_t)std::min<uint64_t>(c->max_rec, p->max_read_size));
+    // the longest read of the short class (160, or 320 where the packed
+    // kernel's mid form takes this call's reads above 160: nw_short_max)
+    const uint64_t xcap_call = std::min<uint64_t>(c->max_rec, p->max_read_size);
+    const uint64_t short_max = nw_short_max(p, xcap_call, ymax);
+    if (!c->is_sub) c->np_mid = short_max > (uint64_t)NW_W / 2;   // this call's slot layout (np_strides)
+    if (!c->is_sub && ymax <= short_max && n) {            // the lanes' shared NW arena, before they start
+        const int rp = np_prepare(c, (uint32_t)xcap_call);
         if (rp) return rp;
     }
     // LANES: the range is cut into `nl` parts that run concurrently on nl
@@ -2529,7 +2597,16 @@ static int align_impl(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint6
     // small NW launches, host round trips -- overlap the others' VALU-bound
     // NW sweeps.  Per-read results do not depend on the cut (reads are
     // independent given the chunk heads).  Short reads only: a long-read
-    // lane's traceback arena takes most of HBM.
+    // lane's traceback arena takes most of HBM.  "Short" is the short class
+    // (short_max): a call whose longest read is a mid read (161 .. 320 bases,
+    // all on the packed kernel) takes lanes like one of 150-base reads.  Its
+    // arenas: the shared one of the non-persistent launches (np_prepare) has
+    // the 19-column form's strides, which exceed the mid shape's (np_strides);
+    // a lane whose launches stay persistent holds an arena of its own of, at
+    // most, 256 CUs x 3 blocks x 4 waves = 3072 slots of the mid shape at
+    // xcap = 3000: (3032 steps x 64 lanes x 3 + 96 checkpoints x 45 x 64)
+    // dwords = 3.43 MB each, 10.6 GB per lane -- 8 lanes (LANES_MAX) 85 GB of
+    // the 288.  mid_lane_cap() cuts the lanes where free HBM is below that.
     // How many: from the work and the hardware queues.  A lane needs
     // LANE_READS reads for its first NW launch to fill the chip's wave slots
     // on its own (~0.9 candidates per read, 8 per wave: 40k reads -> 4.5k
@@ -2548,7 +2625,8 @@ static int align_impl(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint6
     const char *lme = getenv("IMSAME_LANE_MIN");
     const uint64_t lane_min = lme ? strtoull(lme, nullptr, 10) : LANE_MIN;
     while (nl > 1 && n < (uint64_t)nl * lane_min) --nl;
-    if (c->is_sub || c->use_wcap || ymax > (uint64_t)NW_W / 2) nl = 1;
+    if (c->is_sub || c->use_wcap || ymax > short_max) nl = 1;
+    if (nl > 1 && ymax > (uint64_t)NW_W / 2) nl = std::min(nl, mid_lane_cap(c, (uint32_t)xcap_call));
     if (nl == 1) {
         imsame_stats s1{};
         int rc = align_one(c, read_from, read_to, n_threads_semantic, p, res, paths, paths_cap, paths_used, &s1);

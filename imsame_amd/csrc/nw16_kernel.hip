@@ -1,5 +1,5 @@
 // nw16_kernel.hip -- IMSAME's NW + backtracking for short reads (one strip,
-// ylen <= NW_W/2) on PACKED PAIRS: every 32-bit register holds the same cell
+// ylen <= NW16_YMAX) on PACKED PAIRS: every 32-bit register holds the same cell
 // of two candidates, A in bits 0-15 and B in bits 16-31, and the recurrence
 // runs on v_pk_*_i16 / bitwise forms.  Included by imsame_dev.hip (and by
 // tests/emu/wave_emu.cpp under IMSAME_WAVE_EMU) after nw_kernel.hip.
@@ -83,6 +83,13 @@
 #define NW16_K3  3
 #define NW16_K3_YMAX 150          // G <= 50: nw16_ck(3) + G <= 64 (the range proof's extra rows)
 #define NW16_BIG 16384
+// The packed kernel's own bound on a read (the int32 kernel's NW_W/2 = 160 is
+// that kernel's strip geometry, not this one's).  Reads of 161 .. NW16_YMAX
+// bases ("mid" reads) run the 10-column general-length code with G = 17 .. 32
+// lanes per pair (3 pairs per wave up to 210 bases, 2 up to 320) and the MID
+// checkpoint interval below; no other column form takes them.
+#define NW16_YMAX 320
+#define NW16_MID_CK 32
 // Checkpoint interval of the first sweep, per column form (steps; even: the
 // rotation period).  nw16_fits bounds the rows a second sweep runs past the
 // first by CK + G <= 64: K = 5 has G <= 32 (CK 32), K = 10 G <= 16 and K = 19
@@ -90,8 +97,11 @@
 // round 3 wrote 5K+5 every 24 steps (0.46 B/cell at C2), 4K+5 every 48 is
 // ~0.19 B/cell, for ~8 more second-sweep rows per half on average -- only
 // for the halves the first sweep's predicted window does not cover.
-// (K = 3: G <= 50, so CK 14)
-__host__ __device__ constexpr int nw16_ck(int K) { return K <= 3 ? 14 : K <= 5 ? 32 : 48; }
+// (K = 3: G <= 50, so CK 14; MID, the 10-column form of reads of 161-320
+// bases: G <= 32, so CK 32 -- a compile-time variant, not a run-time value)
+__host__ __device__ constexpr int nw16_ck(int K, bool MID = false) {
+    return MID ? NW16_MID_CK : K <= 3 ? 14 : K <= 5 ? 32 : 48;
+}
 // dwords of wave state per lane in a checkpoint (A, B, mcS, u0 per column; I1,
 // I2, outT, outMS, outL); dI is a function of A and I2 there (save())
 __host__ __device__ constexpr int nw16_nst(int K) { return 4 * K + 5; }
@@ -119,19 +129,43 @@ __host__ __device__ constexpr int nw16_nrec(int K) { return K <= 8 ? 2 : K <= 10
 #define NW16_WIN_BOTTOM (-1)
 #define NW16_BAND2 4              // the second sweep's retry band, in bands
 
-// does the launch fit the int16 path?  (all gap terms non-positive)
-__host__ static inline bool nw16_fits(int64_t ig, int64_t eg, uint64_t xcap, uint64_t ymax, int K = NW16_K) {
-    if (ig > 0 || eg > 0 || ymax > (uint64_t)NW_W / 2 || ymax == 0) return false;
+// Mid reads (161 .. NW16_YMAX bases) on the packed kernel: on unless
+// IMSAME_NW_MID=0 (A/B runs, tests; read per call), which brings back the cut
+// at NW_W/2 and the long-read kernels above it.
+__host__ static inline bool nw16_mid_on() {
+    const char *e = getenv("IMSAME_NW_MID");
+    return !(e && !atoi(e));
+}
+// The range proof: do reads up to ymax (<= ybound, the form's longest read)
+// against records up to xcap stay within +-R?  A pure predicate of its
+// arguments (all gap terms non-positive).
+__host__ static inline bool nw16_range_ok(int64_t ig, int64_t eg, uint64_t xcap, uint64_t ymax, int K, uint64_t ybound) {
+    if (ig > 0 || eg > 0 || ymax > ybound || ymax == 0) return false;
     const uint64_t G = (ymax + K - 1) / K, ycols = G * K;
     const uint64_t aig = (uint64_t)(-ig), aeg = (uint64_t)(-eg);
     if (aig > 8191 || aeg > 8191) return false;
     // |T| <= 4*ycols; l0 >= -T - |ig| - |eg|*ycols; u0 drifts at most over
     // xcap + 64 rows (lockstep garbage rows included -- a second sweep runs at
-    // most nw16_ck(K) + G <= 64 rows past the first one)
+    // most CK + G <= 64 rows past the first one: (K, G, CK) = (19, 8, 48),
+    // (10, <= 16, 48), (5, <= 32, 32), (3, <= 50, 14) and, for reads of 161-320
+    // bases, the MID form (10, 17 .. 32, 32))
     // and takes u2 + ig + 2eg.  ycols at K = 10 bounds ycols at K = 5 (K = 19
     // asks with its own ycols; its padding columns never feed a real one).
+    // At the default gaps (-5, -2) the longest mid read and the default record
+    // cap give R = 4*320 + 5 + 2*(3000 + 64 + 322) + 16 = 8073; xcap = 3059 is
+    // the largest cap that fits (R = 8191).
     const uint64_t R = 4 * ycols + aig + aeg * (xcap + 64 + ycols + 2) + 16;
     return R <= 8191;
+}
+// does the launch fit the int16 path?  The proof with the form's bound on a
+// read: NW_W/2, and NW16_YMAX for the 10-column form, the only one with a MID
+// variant -- unless IMSAME_NW_MID=0.  The switch is read here, and only for
+// K = 10, because this is the one function through which every restatement
+// of plan_nw's choice passes: plan_nw, nw_short_max and the CPU emulator's
+// host code, which knows nothing of the switch.
+__host__ static inline bool nw16_fits(int64_t ig, int64_t eg, uint64_t xcap, uint64_t ymax, int K = NW16_K) {
+    const uint64_t ybound = (K == NW16_K && nw16_mid_on()) ? NW16_YMAX : NW_W / 2;
+    return nw16_range_ok(ig, eg, xcap, ymax, K, ybound);
 }
 
 WV_DEVICE uint32_t pk1(int v) { return (uint32_t)(uint16_t)v * 0x10001u; }
@@ -290,9 +324,21 @@ __host__ __device__ static inline size_t nw16_wave_lds(int GPW, int xstride) {
 // equals G*K - OFF), so each candidate's last column is slot K-1 of its owner
 // lane (no select).  OFF: padding columns ahead of column 0 (nw16_k19).
 // TWO: score-only sweep + checkpoints, then the traceback band (header).
-template <int K, bool LAST, bool TWO, int OFF = 0>
+// MID: reads of 161 .. NW16_YMAX bases (K = 10, G = 17 .. 32): the checkpoint
+// interval that keeps CK + G <= 64 (nw16_ck).
+template <int K, bool LAST, bool TWO, int OFF = 0, bool MID = false>
 __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const int lane, const uint32_t slot) {
-    constexpr int NST = nw16_nst(K), NREC = nw16_nrec(K), CK = nw16_ck(K);
+    static_assert(!MID || K == NW16_K, "the mid form is a 10-column form");
+#ifdef IMSAME_WAVE_EMU
+    // The emulator's host code (tests/emu/wave_emu.cpp:run_nw) restates
+    // plan_nw's choice up to <K, LAST, TWO, OFF> and knows no mid kernel: a
+    // 10-column launch shaped for mid reads (nw16_shape: G > 16, checkpoint
+    // words for the 32-step interval) is the mid form's, as on the device.
+    if constexpr (!MID && K == NW16_K && OFF == 0) {
+        if (P.G > NW_W / 2 / NW16_K) { nw16_wave<K, LAST, TWO, OFF, true>(P, wsm, lane, slot); return; }
+    }
+#endif
+    constexpr int NST = nw16_nst(K), NREC = nw16_nrec(K), CK = nw16_ck(K, MID);
     constexpr uint32_t RECB = 64u * 4u * NREC;     // traceback bytes per step
     const int G = P.G, GPW = P.GPW;
     const int g = lane / G, gl = lane - g * G;
@@ -816,6 +862,7 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
 __host__ static inline NwShape nw16_shape(uint32_t ymax, uint32_t xcap, int K = NW16_K) {
     NwShape s;
     s.k = K;
+    s.mid = K == NW16_K && ymax > NW_W / 2;
     s.G = (int)((ymax + K - 1) / K);
     if (s.G < 1) s.G = 1;
     s.GPW = 64 / s.G; s.nstr = 1;
@@ -842,7 +889,16 @@ __host__ static inline bool nw16_k19_ok(uint32_t ylen_uni, uint32_t ymax, uint32
 __host__ static inline uint64_t nw16_tb_words(const NwShape &s) { return (uint64_t)s.steps * 64 * nw16_nrec(s.k); }
 // checkpoint dwords per wave slot (two-pass mode): one per nw16_ck(K) steps + the start
 __host__ static inline uint64_t nw16_ck_words(const NwShape &s) {
-    return (uint64_t)((s.steps + nw16_ck(s.k) - 1) / nw16_ck(s.k) + 1) * nw16_nst(s.k) * 64;
+    const int ck = nw16_ck(s.k, s.mid);
+    return (uint64_t)((s.steps + ck - 1) / ck + 1) * nw16_nst(s.k) * 64;
+}
+// The longest read of a call's short candidate class (the class the packed
+// kernel and the short-read scheduling take): NW16_YMAX where the call has mid
+// reads and the mid form can run a launch of that class -- its longest read
+// min(ycap, NW16_YMAX) against the record cap -- else NW_W/2, as ever.
+__host__ static inline uint32_t nw_short_max(const imsame_params *p, uint64_t xcap, uint64_t ycap) {
+    if (ycap <= (uint64_t)NW_W / 2 || (p->flags & IMSAME_FLAG_NW32)) return NW_W / 2;       // (nw16_fits asks nw16_mid_on)
+    return nw16_fits(p->igap, p->egap, xcap, std::min<uint64_t>(ycap, NW16_YMAX)) ? NW16_YMAX : NW_W / 2;
 }
 
 #ifndef IMSAME_WAVE_EMU
@@ -942,6 +998,30 @@ void nw16_kernel(NwLaunch P) {
         slot = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + wib);   // wave-uniform
     }
     nw16_wave<K, LAST, TWO, OFF>(P, smem + wib * nw16_wave_lds(P.GPW, P.xstride), lane, slot);
+    if (P.slot_bits) nw_slot_release(P, lane, slot);
+}
+// The mid form (reads of 161 .. NW16_YMAX bases): a kernel of its own, so the
+// forms above keep their symbols and their code.  The 10-column form's
+// residency: the checkpoint interval changes no register need.
+#ifndef NW16_MID_WAVES_PER_EU
+#define NW16_MID_WAVES_PER_EU NW16_WAVES_PER_EU
+#endif
+template <bool LAST, bool TWO>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NW16_MID_WAVES_PER_EU)))
+void nw16_mid_kernel(NwLaunch P) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    uint32_t slot;                              // as nw16_kernel
+    if (P.slot_bits) {
+        slot = nw_slot_claim(P, lane);
+        if (slot == ~0u) {
+            if (lane == 0) wv_atomic_or(P.flags, 4u);
+            return;
+        }
+    } else {
+        slot = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + wib);
+    }
+    nw16_wave<NW16_K, LAST, TWO, 0, true>(P, smem + wib * nw16_wave_lds(P.GPW, P.xstride), lane, slot);
     if (P.slot_bits) nw_slot_release(P, lane, slot);
 }
 #endif

@@ -494,7 +494,7 @@ __device__ void nw_wave(const NwLaunch &P, uint8_t *wsm, const int lane, const u
 // Launch shape for reads up to ymax and records up to xcap: short reads pack
 // 64/G candidates per wave, long reads take a wave each over several strips;
 // X staging is capped at 16 KB of LDS per wave.
-struct NwShape { int G, GPW, nstr, xcap, xstride, steps, k = 0; };   // k: nw16 columns per lane
+struct NwShape { int G, GPW, nstr, xcap, xstride, steps, k = 0; bool mid = false; };   // k: nw16 columns per lane (mid: its 161-320-base form)
 __host__ static inline NwShape nw_shape(uint32_t ymax, uint32_t xcap) {
     NwShape s;
     if (ymax <= NW_W / 2) {

@@ -1,5 +1,6 @@
 // nwl_kernel.hip -- IMSAME's NW + backtracking for LONG reads (longer than the
-// packed kernel's 160 columns): one candidate per wave, two passes.  Included
+// packed kernel's NW16_YMAX = 320 columns -- than 160 where its mid form cannot
+// run or IMSAME_NW_MID=0 turns it off): one candidate per wave, two passes.  Included
 // by imsame_dev.hip (and by tests/emu/wave_emu.cpp under IMSAME_WAVE_EMU) after
 // nw_kernel.hip and nw16_kernel.hip.
 //

@@ -1,5 +1,6 @@
 // nwp_kernel.hip -- IMSAME's NW + backtracking for LONG reads (longer than the
-// short kernels' 160 columns) on PACKED PAIRS: two candidates per wave, one in
+// packed short kernel's NW16_YMAX = 320 columns -- than 160 where its mid form
+// cannot run or IMSAME_NW_MID=0 turns it off) on PACKED PAIRS: two candidates per wave, one in
 // each int16 half of every register, over nwl_kernel.hip's strips, seams,
 // checkpoints and bands.  Included by imsame_dev.hip (and by
 // tests/emu/wave_emu.cpp under IMSAME_WAVE_EMU) after nwl_kernel.hip.

@@ -22,14 +22,16 @@ struct RoundPolicy {
     uint32_t grow = 8;
     uint64_t l64_below = 8192;       // reads (over all lanes) below which a whole wave scans a read
     int nlanes = 1;                  // lanes of the call: the device scans nlanes x na reads at once
-    bool r1b_on = true;              // round 1b (short reads only)
-    bool split_on = true;            // split rounds (imsame_dev.hip:align_one; short reads only)
+    bool r1b_on = true;              // round 1b (calls of the short class only: ycap <= short_y)
+    bool split_on = true;            // split rounds (imsame_dev.hip:align_one; the short class only)
     uint32_t split_min = 16384;      // ... of at least this many active reads
     bool window = true;              // predicted traceback windows of the packed NW kernel
     bool weak_rows = false;          // ... predicted from weak hits too (IMSAME_NW_WEAK_ROWS)
     bool r1b_rows = false;           // ... for round 1b's candidates (IMSAME_NW_R1B_ROWS)
 
-    // A lane's call of n reads whose longest is ycap (short reads: <= short_y).
+    // A lane's call of n reads whose longest is ycap (the short class: <= short_y,
+    // nw16_kernel.hip:nw_short_max -- 160 bases, or 320 where the packed
+    // kernel's mid form takes the call).
     // Environment overrides (A/B runs, tests): IMSAME_SPEC_WEAK, IMSAME_CCAP_MULT,
     // IMSAME_SPEC, IMSAME_SEED_BUDGET, IMSAME_SEED_GROW, IMSAME_SEED_L64,
     // IMSAME_ROUND1B, IMSAME_NW_WINDOW.

@@ -128,7 +128,9 @@ typedef struct imsame_stats {
                                traceback band missed a path (4 bands, then
                                from row 1)                                  */
     uint64_t launch_pk;     /* bit k: NW launch k ran the packed int16 kernel
-                               (nw16_kernel), else the int32 nw_kernel     */
+                               (nw16_kernel; reads of 161-320 bases its mid
+                               form: launch_k5, _k3 and _k19 clear), else the
+                               int32 nw_kernel or a long-read kernel       */
     uint64_t nw_win;        /* two-pass NW: candidates whose path was walked in
                                the first sweep's predicted traceback window  */
     double   ms_nw_first;   /* first NW launch start / last NW launch end, ms
@@ -143,7 +145,9 @@ typedef struct imsame_stats {
                                150: every lane of the wave busy)          */
     uint64_t launch_nwp;    /* bit k: NW launch k ran the packed long-read
                                kernel (two long reads per wave, int16
-                               halves in per-lane frames)                 */
+                               halves in per-lane frames): reads above 320
+                               bases, or above 160 where the packed short
+                               kernel's mid form cannot take the launch   */
     uint64_t nw_fallback;   /* packed long-read waves whose values left the
                                int16 range proof: their pairs ran the int32
                                long-read path instead (same results)      */
@@ -263,7 +267,10 @@ int imsame_dev_sync(imsame_ctx *ctx);
  * complete below the offending read -- so callers compare *paths_used with
  * paths_cap whatever the code, grow the host arena and call
  * imsame_dev_fetch_paths.
- * A call over short reads is cut into up to 8 parts ("lanes") that run
+ * A call whose longest read is a short one -- up to 160 bases, or up to 320
+ * where the packed kernel's mid form takes the call's reads (default gaps,
+ * records up to 3059 bases; IMSAME_NW_MID=0 turns that off) -- is cut into up
+ * to 8 parts ("lanes") that run
  * concurrently on their own streams (internal contexts sharing the index
  * and the query): one lane per 40,000 reads, at most one per hardware queue
  * (GPU_MAX_HW_QUEUES, see imsame_dev_open).  Results do not depend on it
