@@ -363,6 +363,8 @@ struct imsame_ctx {
     DBuf ctr;
     // tables (and the inputs they were built for)
     DBuf minraw, minlen, minident;
+    DBuf bmin;                        // nw16's stop: nw16_bmin per read length, for tab_ig / tab_eg
+    int64_t tab_ig = 0, tab_eg = 0;
     bool tab_valid = false;
     long double tab_min_e = 0, tab_cov = 0, tab_id = 0;
     uint64_t tab_L = 0;
@@ -451,7 +453,7 @@ static inline const uint64_t *dev_qs(const imsame_ctx *c) {
 // counters block layout (u64 slots)
 enum { C_NCAND = 0, C_NCAND2, C_NNEXT, C_NCANDB, C_NCAND2B, C_NNEXT2, C_WORKB,   // (round 1b: B, 2)
        C_WORK, C_WORK2, C_PATHS, C_FLAGS, C_ERR, C_HITS, C_CELLS, C_NACC, C_REDO,
-       C_PROF, C_WIN = C_PROF + 14, C_FBK, C_SWORK, C_DBG = C_SWORK + 3, C_WASTE = C_DBG + 8,
+       C_PROF, C_WIN = C_PROF + 16, C_FBK, C_SWORK, C_DBG = C_SWORK + 3, C_WASTE = C_DBG + 8,
        C_NSLOTS };
 
 // IMSAME_DEBUG_STALL=A:<us>|B:<us>[,...] (tests of the order between a lane's
@@ -741,7 +743,7 @@ extern "C" void imsame_dev_close(imsame_ctx *c) {
     DBuf *bufs[] = {&c->db, &c->db_start, &c->off, &c->ent, &c->brk, &c->codes, &c->fill, &c->big, &c->q,
                     &c->q_start, &c->res, &c->cur_p, &c->cur_h, &c->memo, &c->nmemo, &c->rstat, &c->act0,
                     &c->act1, &c->cread, &c->csid, &c->cread2, &c->csid2, &c->cout, &c->cout2, &c->ctr,
-                    &c->minraw, &c->minlen, &c->minident, &c->tb, &c->bnd, &c->paths, &c->ck, &c->rc_in, &c->rc_out,
+                    &c->minraw, &c->minlen, &c->minident, &c->bmin, &c->tb, &c->bnd, &c->paths, &c->ck, &c->rc_in, &c->rc_out,
                     &c->rc_a, &c->rc_b, &c->rc_c, &c->cbase, &c->ccnt, &c->perr, &c->wcap, &c->wout, &c->wstart,
                     &c->crow, &c->cperm, &c->rhist, &c->act2, &c->act3, &c->slotbits, &c->np_tb, &c->np_ck, &c->dbw, &c->qw,
                     &c->cperm_b, &c->rhist_b};
@@ -1082,14 +1084,18 @@ static int build_tables(imsame_ctx *c, const imsame_params *p, uint32_t ymax, ui
     // them across calls (ymax = 10,000 takes ~0.1 s of x87 expl / divisions)
     const uint64_t L = c->ev_db_len ? c->ev_db_len : c->db_len;
     if (c->tab_valid && c->tab_min_e == p->min_e && c->tab_cov == p->min_coverage && c->tab_id == p->min_identity &&
-        c->tab_L == L && c->tab_ymax == ymax && c->tab_xmax == xmax)
+        c->tab_L == L && c->tab_ymax == ymax && c->tab_xmax == xmax && c->tab_ig == p->igap && c->tab_eg == p->egap)
         return 0;
     c->tab_valid = false;
     std::vector<uint64_t> mr;
     std::vector<uint32_t> ml, mi;
     imsame_build_tables(p, c->ev_db_len ? c->ev_db_len : c->db_len, ymax, xmax, mr, ml, mi);
-    if (c->minraw.ensure(mr.size() * 8) || c->minlen.ensure(ml.size() * 4) || c->minident.ensure(mi.size() * 4))
+    std::vector<int32_t> bm((size_t)ymax + 1);
+    nw16_bmin_table(ymax, p->igap, p->egap, bm.data());
+    if (c->minraw.ensure(mr.size() * 8) || c->minlen.ensure(ml.size() * 4) || c->minident.ensure(mi.size() * 4) ||
+        c->bmin.ensure(bm.size() * 4))
         return IMSAME_E_OOM;
+    HIPCHK(hipMemcpyAsync(c->bmin.p, bm.data(), bm.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->minraw.p, mr.data(), mr.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->minlen.p, ml.data(), ml.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->minident.p, mi.data(), mi.size() * 4, hipMemcpyHostToDevice, c->stream));
@@ -1097,6 +1103,7 @@ static int build_tables(imsame_ctx *c, const imsame_params *p, uint32_t ymax, ui
     c->tab_valid = true;
     c->tab_min_e = p->min_e; c->tab_cov = p->min_coverage; c->tab_id = p->min_identity;
     c->tab_L = L; c->tab_ymax = ymax; c->tab_xmax = xmax;
+    c->tab_ig = p->igap; c->tab_eg = p->egap;
     return 0;
 }
 
@@ -1560,6 +1567,10 @@ static int launch_nw(imsame_ctx *c, NwPlan &pl, const uint32_t *cread, const uin
     P.band_w = pl.band_w; P.redo = (uint32_t *)(ctr + C_REDO); P.win = (uint32_t *)(ctr + C_WIN);
     P.prof = getenv("IMSAME_NW_PROF") ? (unsigned long long *)(ctr + C_PROF) : nullptr;
     P.slot_bits = pl.np ? ao->slotbits.as<uint32_t>() : nullptr; P.slot_words = pl.slot_words;
+    // nw16's first-sweep stop: the table of this call's gaps (build_tables)
+    P.bmin = c->bmin.as<int32_t>();
+    P.stop_off = !(nw16_stop_env() && pl.pk && c->tab_valid && c->tab_ig == ig && c->tab_eg == eg && ymax <= c->tab_ymax &&
+                   nw16_bmin(ymax, ig, eg) != INT32_MAX);
     STALL(c, s);                                 // (ahead of e0: not in the launch's time)
     HIPCHK(hipMemsetAsync(work, 0, 4, s));
     HIPCHK(hipEventRecord(e0, s));               // the launch's time includes its ordering
@@ -2451,11 +2462,13 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
         const double ghz = hc[C_PROF + 5] ? tot / (double)hc[C_PROF + 5] * 0.1 : 0.0;
         fprintf(stderr, "[nwprof] setup %.3f sweep1 %.3f reduce %.3f sweep2 %.3f walk %.3f (fractions of %.4g wave-cycles) "
                 "clock_ghz %.3f best_cells(weak: last_row last_col<=40 <=200 higher | predicted: in out) "
-                "%llu %llu %llu %llu | %llu %llu weak_window_waves(all skipped_second_sweep) %llu %llu\n", hc[C_PROF] / tot, hc[C_PROF + 1] / tot, hc[C_PROF + 2] / tot,
+                "%llu %llu %llu %llu | %llu %llu weak_window_waves(all skipped_second_sweep) %llu %llu "
+                "stop(waves steps_skipped) %llu %llu\n", hc[C_PROF] / tot, hc[C_PROF + 1] / tot, hc[C_PROF + 2] / tot,
                 hc[C_PROF + 3] / tot, hc[C_PROF + 4] / tot, tot, ghz, (unsigned long long)hc[C_PROF + 6],
                 (unsigned long long)hc[C_PROF + 7], (unsigned long long)hc[C_PROF + 8], (unsigned long long)hc[C_PROF + 9],
                 (unsigned long long)hc[C_PROF + 10], (unsigned long long)hc[C_PROF + 11],
-                (unsigned long long)hc[C_PROF + 12], (unsigned long long)hc[C_PROF + 13]);
+                (unsigned long long)hc[C_PROF + 12], (unsigned long long)hc[C_PROF + 13],
+                (unsigned long long)hc[C_PROF + 14], (unsigned long long)hc[C_PROF + 15]);
     }
     if ((c->stall_us[0] || c->stall_us[1]) && getenv("IMSAME_DEBUG_ROUNDS"))
         fprintf(stderr, "[stall] A=%u B=%u\n", c->stall_n[0], c->stall_n[1]);

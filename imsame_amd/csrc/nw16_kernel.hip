@@ -168,6 +168,57 @@ __host__ static inline bool nw16_fits(int64_t ig, int64_t eg, uint64_t xcap, uin
     return nw16_range_ok(ig, eg, xcap, ymax, K, ybound);
 }
 
+// The first sweep's stop (header of nw16_wave's setup).  The
+// record is probed for the read's NW16_STOP_MER-mers at every
+// NW16_STOP_STRIDE-th row only (rows = 0 mod the stride): a diagonal run of
+// NW16_STOP_RUN = MER + STRIDE - 1 matches holds a probed row with its whole
+// 12-mer inside the run, so below the last probed hit no such run starts.  A
+// chain of cells without a run of NW16_STOP_RUN matches scores at most
+// nw16_bmin - 1: with x mismatches and g jumps its matches m come in at most
+// x + g + 1 runs of at most RUN - 1, its cells m + x take distinct columns,
+// and a jump costs at least |ig| + |eg|:
+//     max 4m - 4x - (|ig| + |eg|) g,  m <= 14 (x + g + 1),  m + x <= ylen.
+// (Stride 1 is the plain form, runs of 12 and 510 at the default gaps and 150
+// bases; stride 4 probes a quarter of the rows for a bmin of 531, which a read
+// passes with up to 8 substitutions.)
+// INT32_MAX (never reached: the stop is off) for gaps the argument does not
+// cover: eg = 0, where rows can be skipped for nothing, or a positive gap.
+#define NW16_STOP_MER 12
+#define NW16_STOP_STRIDE 4
+#define NW16_STOP_RUN (NW16_STOP_MER + NW16_STOP_STRIDE - 1)
+__host__ static inline int32_t nw16_bmin(int64_t ylen, int64_t ig, int64_t eg) {
+    // (only the packed kernel's reads: the loops below are ~ylen^2 / 22 steps)
+    if (eg >= 0 || ig > 0 || ylen < NW16_STOP_MER || ylen > NW16_YMAX || ig < -8191 || eg < -8191) return INT32_MAX;
+    const int64_t c = -(ig + eg);
+    int64_t best = INT64_MIN;
+    for (int64_t x = 0; x <= ylen; ++x)
+        for (int64_t g = 0; g <= ylen; ++g) {
+            const int64_t m = std::min<int64_t>(ylen - x, (NW16_STOP_RUN - 1) * (x + g + 1));
+            best = std::max(best, 4 * m - 4 * x - c * g);
+            if ((NW16_STOP_RUN - 1) * (x + g + 1) >= ylen - x) break;      // more jumps only cost
+        }
+    return (int32_t)(best + 1);
+}
+// the table of a launch's read lengths (NwLaunch::bmin)
+__host__ static inline void nw16_bmin_table(uint32_t ymax, int64_t ig, int64_t eg, int32_t *out) {
+    for (uint32_t y = 0; y <= ymax; ++y) out[y] = nw16_bmin(y, ig, eg);
+}
+// IMSAME_NW_STOP=0 turns the stop off (A/B runs, tests; read per call)
+__host__ static inline bool nw16_stop_env() {
+    const char *e = getenv("IMSAME_NW_STOP");
+    return !(e && !atoi(e));
+}
+#ifdef IMSAME_WAVE_EMU
+// the emulator's counters: waves that stopped, steps they skipped (the
+// device's are P.prof [14], [15]); read and cleared
+static std::atomic<uint64_t> g_nw16_stop_waves{0}, g_nw16_stop_steps{0};
+extern "C" void emu_nw16_stop_counts(uint64_t *waves, uint64_t *steps) {
+    if (waves) *waves = g_nw16_stop_waves.exchange(0);
+    if (steps) *steps = g_nw16_stop_steps.exchange(0);
+}
+extern "C" int32_t emu_nw16_bmin(int64_t ylen, int64_t ig, int64_t eg) { return nw16_bmin(ylen, ig, eg); }
+#endif
+
 WV_DEVICE uint32_t pk1(int v) { return (uint32_t)(uint16_t)v * 0x10001u; }
 WV_DEVICE uint32_t pk2(int lo, int hi) { return (uint32_t)(uint16_t)lo | ((uint32_t)(uint16_t)hi << 16); }
 WV_DEVICE int pk_half(uint32_t v, int h) { return (int)(int16_t)(h ? (v >> 16) : (v & 0xFFFFu)); }
@@ -356,6 +407,33 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
     auto mark = [&](const int k) {
         if (P.prof) { const unsigned long long n = wv_clock(); ph[k] += n - tq; tq = n; }
     };
+    // The first sweep's stop (TWO, predicted candidates).  A cell's value is
+    // the score of a chain of cells from row 0 or column 0: columns rise, rows
+    // never fall, each cell adds +-4, each jump costs |ig| + |eg| at least and
+    // |eg| per skipped row, so a chain of L <= ylen cells that skips S rows
+    // spans at most L - 1 + S rows.  With `clear` = 1 + the last probed record
+    // row (every NW16_STOP_STRIDE-th) where a NW16_STOP_MER-mer of the read
+    // starts (0: none) and B a value the last column holds already:
+    //   a chain that starts at a row >= clear has no run of NW16_STOP_RUN
+    //     matches and scores < bmin[ylen] (nw16_bmin), so < B once B >= bmin;
+    //   a chain from above `clear` that ends on row i skips S >= i - clear + 2 -
+    //     ylen rows and scores <= 4 ylen - |eg| S, so < B on every row
+    //     i > clear - 2 + ylen + (4 ylen - B) / |eg|.
+    // Past that row neither the last column nor the last row reaches B (a
+    // strict <, as the ">=" tie rule needs): the best cell is final and lies
+    // in the last column.  `clear` comes from a table of the read's 12-mers in
+    // the half's share of the LDS record area, built and probed BEFORE the
+    // record is staged; launches whose share cannot hold the table at load
+    // factor 0.6 (short records, the mid form) run without the stop.
+    const int stop_slots = (P.xstride / 8) & ~3;   // dword slots per half, in buckets of four (one 16-byte LDS read)
+    bool stopf = TWO && !P.stop_off && P.cand_row && eg < 0 && ig <= 0 && G * K - OFF >= NW16_STOP_MER &&
+                 10 * (G * K - OFF - (NW16_STOP_MER - 1)) <= 6 * stop_slots;
+#ifdef IMSAME_WAVE_EMU
+    stopf = stopf && nw16_stop_env();
+#else
+    stopf = stopf && P.bmin;
+#endif
+    const int aeg = -eg;
     for (uint32_t ntask = 0;; ++ntask) {
         if (P.slot_bits && ntask) break;          // non-persistent launch: one task per wave
         uint32_t base = 0;
@@ -397,6 +475,137 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
         // an idle group (no candidate) reads group 0's record, so its lockstep
         // garbage stays a bounded DP like everyone else's
         uint8_t *X8 = wsm + (size_t)(valid[0] ? g : 0) * P.xstride;
+        // the stop: only a wave whose every candidate is predicted (a weak
+        // hit's best cell mostly sits on the last row, below bmin) and long
+        // enough to hold a 12-mer
+        bool can_stop = false;
+        if (stopf) {
+            bool scan[2], bad = false;
+            for (int h = 0; h < 2; ++h) {
+                scan[h] = valid[h] && prow[h] != NW16_NOROW && yl[h] >= NW16_STOP_MER;
+                bad = bad || (valid[h] && !scan[h]);
+            }
+            can_stop = !wv_any(bad) && wv_any(scan[0]);
+            if (can_stop) {
+                constexpr uint32_t EMPTY = 0xFFFFFFFFu, CMASK = (1u << (2 * NW16_STOP_MER)) - 1u;
+                const uint32_t ns = (uint32_t)stop_slots;
+                uint32_t *tab = (uint32_t *)X8;                   // half h: slots [h * ns, (h + 1) * ns)
+                const uint32_t nb = ns / 4;
+                auto bucket_of = [&](const uint32_t code) { return (((code * 0x9E3779B1u) >> 16) * nb) >> 16; };
+                if (valid[0])
+                    for (uint32_t k = (uint32_t)gl; k < 2 * ns; k += (uint32_t)G) tab[k] = EMPTY;
+                wv_lds_sync();
+                for (int h = 0; h < 2; ++h) {
+                    if (!scan[h]) continue;
+                    // a contiguous share of the read's 12-mers per lane, one rolling code
+                    const int nk = yl[h] - (NW16_STOP_MER - 1), per = (nk + G - 1) / G;
+                    const int k0 = gl * per, k1 = min(nk, k0 + per);
+                    uint32_t code = 0;
+                    for (int b = k0; b < k1 + NW16_STOP_MER - 1; ++b) {
+                        code = ((code << 2) | base_code(Yp[h][b])) & CMASK;
+                        if (b < k0 + NW16_STOP_MER - 1) continue;
+                        // the first free slot from the home bucket's first on: every slot
+                        // before it is taken for good, so a probe that walks the buckets
+                        // from the home one meets the code before it meets a free slot
+                        for (uint32_t sl = 4u * bucket_of(code);;) {
+                            const uint32_t old = wv_lds_cas(tab + h * ns + sl, EMPTY, code);
+                            if (old == EMPTY || old == code) break;
+                            if (++sl == ns) sl = 0;
+                        }
+                    }
+                }
+                wv_lds_sync();
+                // the record's rows from the bottom up, G * 32 per block, 32 per lane,
+                // of which every NW16_STOP_STRIDE-th is probed; row i holds a 12-mer
+                // if i <= xlen - 12, and `top` (a multiple of the stride, like every
+                // lane's r0) lies just above the last probed row
+                constexpr int LROWS = 32;                             // rows per lane and block
+                constexpr int NPR = LROWS / NW16_STOP_STRIDE;         // ... of which it probes NPR,
+                constexpr int LBYTES = LROWS - NW16_STOP_STRIDE + NW16_STOP_MER;   // whose 12-mers take LBYTES bytes
+                static_assert(LROWS % NW16_STOP_STRIDE == 0 && LBYTES % 4 == 0, "whole dwords");
+                int top[2], clr[2] = {0, 0};
+                bool act[2];
+                for (int h = 0; h < 2; ++h) {
+                    top[h] = xl[h] >= NW16_STOP_MER ? (xl[h] - NW16_STOP_MER) / NW16_STOP_STRIDE * NW16_STOP_STRIDE + NW16_STOP_STRIDE : 0;
+                    act[h] = scan[h] && top[h] > 0;
+                }
+                while (wv_any(act[0] || act[1])) {
+                    // the codes of both halves' probed rows and the home bucket of each
+                    uint32_t code[2][NPR], bk0[2][NPR];
+                    int r0[2];
+                    for (int h = 0; h < 2; ++h) {
+                        r0[h] = top[h] - (gl + 1) * LROWS;            // rows [r0, r0 + LROWS), bytes [r0, r0 + LBYTES)
+                        const bool on = act[h] && r0[h] + LROWS > 0;
+                        uint32_t w[LBYTES / 4] = {};
+                        if (on && r0[h] >= 0) {                       // (r0 + LBYTES <= xlen: the last probed 12-mer ends there)
+                            __builtin_memcpy(w, Xg[h] + r0[h], LBYTES);
+                        } else if (on) {
+#pragma unroll
+                            for (int q = 0; q < LBYTES / 4; ++q) {
+                                uint32_t v = 0;
+#pragma unroll
+                                for (int b = 0; b < 4; ++b)
+                                    v |= (uint32_t)Xg[h][min(max(r0[h] + 4 * q + b, 0), xl[h] - 1)] << (8 * b);
+                                w[q] = v;
+                            }
+                        }
+                        uint32_t c = 0;
+#pragma unroll
+                        for (int b = 0; b < LBYTES; ++b) {
+                            c = ((c << 2) | ((w[b >> 2] >> (8 * (b & 3) + 1)) & 3u)) & CMASK;
+                            if (b < NW16_STOP_MER - 1 || (b - (NW16_STOP_MER - 1)) % NW16_STOP_STRIDE) continue;
+                            const int k = (b - (NW16_STOP_MER - 1)) / NW16_STOP_STRIDE;
+                            code[h][k] = c; bk0[h][k] = bucket_of(c);
+                        }
+                        if (!on) r0[h] = INT_MIN / 2;                 // every row of it "above the record"
+                    }
+                    for (int h = 0; h < 2; ++h) {
+                        // a half's home buckets read together (one LDS round trip for the
+                        // probes that end there: the bucket holds the code, or a free slot)
+                        uint4 v0[NPR];
+#pragma unroll
+                        for (int k = 0; k < NPR; ++k) v0[k] = *(const uint4 *)(tab + h * ns + 4u * bk0[h][k]);
+                        int hit = -1;
+#pragma unroll
+                        for (int k = 0; k < NPR; ++k) {
+                            const int row = r0[h] + k * NW16_STOP_STRIDE;
+                            if (row < 0) continue;
+                            const uint32_t c = code[h][k];
+                            uint32_t b = bk0[h][k];
+                            uint4 v = v0[k];
+                            for (;;) {
+                                if (v.x == c || v.y == c || v.z == c || v.w == c) { hit = row; break; }
+                                if (v.x == EMPTY || v.y == EMPTY || v.z == EMPTY || v.w == EMPTY) break;
+                                if (++b == nb) b = 0;
+                                v = *(const uint4 *)(tab + h * ns + 4u * b);
+                            }
+                        }
+                        red[lane * 8 + 4 * h + 2] = hit;
+                    }
+                    wv_lds_sync();
+                    for (int h = 0; h < 2; ++h) {
+                        if (!act[h]) continue;
+                        int m = -1;
+                        for (int k = 0; k < G; ++k) m = max(m, red[(g * G + k) * 8 + 4 * h + 2]);
+                        if (m >= 0) { clr[h] = m + 1; act[h] = false; }
+                        else if ((top[h] -= G * LROWS) <= 0) act[h] = false;
+                    }
+                    wv_lds_sync();
+                }
+                // the lane's two free slots of each half (until the reduction): the
+                // row formula's constant part and bmin, read back at checkpoints
+                for (int h = 0; h < 2; ++h) {
+#ifdef IMSAME_WAVE_EMU
+                    const int bm = !scan[h] ? INT_MAX : P.bmin ? P.bmin[yl[h]] : nw16_bmin(yl[h], ig, eg);
+#else
+                    const int bm = scan[h] ? P.bmin[yl[h]] : INT_MAX;
+#endif
+                    red[lane * 8 + 4 * h + 2] = clr[h] - 2 + yl[h];
+                    red[lane * 8 + 4 * h + 3] = bm;
+                }
+                wv_lds_sync();                    // the tables are read: the record may take their place
+            }
+        }
         if (valid[0]) {
             // 16 rows per lane and iteration: one unaligned 16-byte load per record
             // where the chunk lies inside it (else bytes clamped to its last base),
@@ -633,6 +842,26 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
             p[(4 * K + 2) * 64] = outT; p[(4 * K + 3) * 64] = outMS; p[(4 * K + 4) * 64] = outL;
         };
         int nextck = 1 + CK, mck = 1;
+        // The stop test, at checkpoint steps only and OUTSIDE the sweep loops
+        // (pairs() leaves its loop at step tstop, tests, and goes back in; the
+        // loops are the ones they were).  Before step t the rows < t - (G - 1)
+        // are done in every lane: each half's last-column owner checks its B
+        // >= bmin and t - (G - 1) past the formula's row, the wave votes, and
+        // the window, if there is one, must be written to its end (the walks
+        // read it).  The checkpoints a second sweep restarts from lie above
+        // the best cell, so they are all saved by now.
+        bool stopped = false;
+        int tstop = (int)wv_first((uint32_t)(can_stop ? 1 + CK : INT_MAX - 2));
+        auto stop_now = [&](const int t) {
+            if (tw1 > tw0 && t < tw1) return false;
+            bool bad = false;
+            for (int h = 0; h < 2; ++h) {
+                if (!(valid[h] && ownC[h])) continue;
+                const int Bv = pk_score(bestC, h), base = red[lane * 8 + 4 * h + 2], bm = red[lane * 8 + 4 * h + 3];
+                bad = bad || Bv < bm || aeg * (t - (G - 1) - base) <= 4 * yl[h] - Bv;
+            }
+            return !wv_any(bad);
+        };
         auto ck = [&](const int t) { if (TWO && t == nextck) { save(mck); ++mck; nextck += CK; } };
         if (TWO) save(0);
         mark(0);
@@ -645,12 +874,23 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
             // each loop is a scalar one (counter, checkpoint test and branch in SGPRs)
             t = (int)wv_first((uint32_t)t);
             const int tl = (int)wv_first((uint32_t)tlim);
-            for (; t + 1 <= tl; t += 2) {
-                ck(t);
-                step(HEAD, TAIL, TBW, t, A, B, I2, I1);
-                if (TAIL) rowbest(t, A);
-                step(HEAD, TAIL, TBW, t + 1, B, A, I1, I2);
-                if (TAIL) rowbest(t + 1, B);
+            if (stopped) return;
+            for (;;) {
+                // (said again: the inner loop's counter, bound and checkpoint test stay scalar)
+                t = (int)wv_first((uint32_t)t);
+                nextck = (int)wv_first((uint32_t)nextck); mck = (int)wv_first((uint32_t)mck);
+                const int tb = (int)wv_first((uint32_t)min(tl, tstop - 1));
+                for (; t + 1 <= tb; t += 2) {
+                    ck(t);
+                    step(HEAD, TAIL, TBW, t, A, B, I2, I1);
+                    if (TAIL) rowbest(t, A);
+                    step(HEAD, TAIL, TBW, t + 1, B, A, I1, I2);
+                    if (TAIL) rowbest(t + 1, B);
+                }
+                if (t + 1 > tl) break;
+                // t == tstop, a checkpoint step (both = 1 mod CK)
+                if (wv_first(stop_now(t) ? 1u : 0u)) { stopped = true; break; }
+                tstop += CK;
             }
         };
         // pairs up to step tlim: before, inside and after the window as three
@@ -671,7 +911,16 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
         sweep(true, true, thead);
         sweep(false, false, xmin - 2);
         sweep(false, true, tpair);
-        if (t < tend) {
+        if (stopped) {
+            // the steps left out, the odd last one and rowbest() among them: the
+            // last row's slots keep INT_MIN, below any last-column value
+            if (lane == 0) {
+                if (P.prof) { wv_atomic_add64(P.prof + 14, 1ull); wv_atomic_add64(P.prof + 15, (unsigned long long)(tend - t)); }
+#ifdef IMSAME_WAVE_EMU
+                ++g_nw16_stop_waves; g_nw16_stop_steps += (uint64_t)(tend - t);
+#endif
+            }
+        } else if (t < tend) {
             if (TWO && t >= tw0 && t < tw1) step(true, true, true, t, A, B, I2, I1);
             else                            step(true, true, TB1, t, A, B, I2, I1);
             rowbest(t, A);

@@ -80,6 +80,11 @@ struct NwLaunch {
     // through the int32 nwl_cand instead)
     int32_t rlim, nwp_s;
     uint32_t *fbk;
+    // nw16 first-sweep stop (nw16_kernel.hip): bmin[ylen] of the launch's gaps
+    // (nw16_bmin; NULL under the emulator: computed there), and the switch --
+    // 0 = on, so a zeroed launch runs it
+    const int32_t *bmin;
+    int32_t stop_off;
 };
 
 // LDS bytes one wave needs

@@ -40,6 +40,8 @@ WV_DEVICE uint32_t wv_atomic_add(uint32_t *p, uint32_t v) { return atomicAdd(p, 
 WV_DEVICE void wv_atomic_or(uint32_t *p, uint32_t v) { atomicOr(p, v); }
 WV_DEVICE void wv_atomic_min64(unsigned long long *p, unsigned long long v) { atomicMin(p, v); }
 WV_DEVICE void wv_atomic_add64(unsigned long long *p, unsigned long long v) { atomicAdd(p, v); }
+// compare-and-swap on an LDS dword (ds_cmpst_rtn_b32): the value found
+WV_DEVICE uint32_t wv_lds_cas(uint32_t *p, uint32_t expect, uint32_t v) { return atomicCAS(p, expect, v); }
 // shader clock (phase profiling only)
 WV_DEVICE unsigned long long wv_clock() { return (unsigned long long)clock64(); }
 // the constant 100 MHz counter (s_memrealtime): with wv_clock it gives the shader clock
@@ -132,6 +134,7 @@ WV_DEVICE uint32_t wv_shift_in(uint32_t w, bool c) {
 using std::max;
 using std::min;
 struct uint2 { uint32_t x, y; };
+struct alignas(16) uint4 { uint32_t x, y, z, w; };
 inline uint2 make_uint2(uint32_t x, uint32_t y) { return uint2{x, y}; }
 
 namespace wvemu {
@@ -201,6 +204,10 @@ inline void wv_atomic_min64(unsigned long long *p, unsigned long long v) {
     while (v < cur && !__atomic_compare_exchange_n(p, &cur, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {}
 }
 inline void wv_atomic_add64(unsigned long long *p, unsigned long long v) { __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
+inline uint32_t wv_lds_cas(uint32_t *p, uint32_t expect, uint32_t v) {
+    __atomic_compare_exchange_n(p, &expect, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST);
+    return expect;
+}
 inline unsigned long long wv_clock() { return 0; }
 inline unsigned long long wv_realtime() { return 0; }
 inline void wv_lds_sync() { wvemu::sync(); }
