@@ -453,7 +453,7 @@ static inline const uint64_t *dev_qs(const imsame_ctx *c) {
 // counters block layout (u64 slots)
 enum { C_NCAND = 0, C_NCAND2, C_NNEXT, C_NCANDB, C_NCAND2B, C_NNEXT2, C_WORKB,   // (round 1b: B, 2)
        C_WORK, C_WORK2, C_PATHS, C_FLAGS, C_ERR, C_HITS, C_CELLS, C_NACC, C_REDO,
-       C_PROF, C_WIN = C_PROF + 16, C_FBK, C_SWORK, C_DBG = C_SWORK + 3, C_WASTE = C_DBG + 8,
+       C_PROF, C_WIN = C_PROF + 21, C_FBK, C_SWORK, C_DBG = C_SWORK + 3, C_WASTE = C_DBG + 8,
        C_NSLOTS };
 
 // IMSAME_DEBUG_STALL=A:<us>|B:<us>[,...] (tests of the order between a lane's
@@ -2469,6 +2469,10 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
                 (unsigned long long)hc[C_PROF + 10], (unsigned long long)hc[C_PROF + 11],
                 (unsigned long long)hc[C_PROF + 12], (unsigned long long)hc[C_PROF + 13],
                 (unsigned long long)hc[C_PROF + 14], (unsigned long long)hc[C_PROF + 15]);
+        // phase 0 ("setup") in its five parts, as fractions of the same total
+        fprintf(stderr, "[nwprof-setup] fetch %.4f table %.4f scan %.4f staging %.4f columns %.4f (fractions of %.4g wave-cycles)\n",
+                hc[C_PROF + 16] / tot, hc[C_PROF + 17] / tot, hc[C_PROF + 18] / tot, hc[C_PROF + 19] / tot,
+                hc[C_PROF + 20] / tot, tot);
     }
     if ((c->stall_us[0] || c->stall_us[1]) && getenv("IMSAME_DEBUG_ROUNDS"))
         fprintf(stderr, "[stall] A=%u B=%u\n", c->stall_n[0], c->stall_n[1]);

@@ -186,6 +186,10 @@ __host__ static inline bool nw16_fits(int64_t ig, int64_t eg, uint64_t xcap, uin
 #define NW16_STOP_MER 12
 #define NW16_STOP_STRIDE 4
 #define NW16_STOP_RUN (NW16_STOP_MER + NW16_STOP_STRIDE - 1)
+// a wave that has no checkpoint step at which it could stop skips the stop's setup
+#ifndef NW16_SKIP_NOSTOP
+#define NW16_SKIP_NOSTOP 1
+#endif
 __host__ static inline int32_t nw16_bmin(int64_t ylen, int64_t ig, int64_t eg) {
     // (only the packed kernel's reads: the loops below are ~ylen^2 / 22 steps)
     if (eg >= 0 || ig > 0 || ylen < NW16_STOP_MER || ylen > NW16_YMAX || ig < -8191 || eg < -8191) return INT32_MAX;
@@ -407,6 +411,12 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
     auto mark = [&](const int k) {
         if (P.prof) { const unsigned long long n = wv_clock(); ph[k] += n - tq; tq = n; }
     };
+    // phase 0 in five parts (P.prof [16 .. 20]): candidate fetch, stop table
+    // build, stop scan, staging, column codes + row-0 state + save(0)
+    unsigned long long sp[5] = {0, 0, 0, 0, 0}, sq = 0;
+    auto smark = [&](const int k) {
+        if (P.prof) { const unsigned long long n = wv_clock(); sp[k] += n - sq; sq = n; }
+    };
     // The first sweep's stop (TWO, predicted candidates).  A cell's value is
     // the score of a chain of cells from row 0 or column 0: columns rise, rows
     // never fall, each cell adds +-4, each jump costs |ig| + |eg| at least and
@@ -436,34 +446,73 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
     const int aeg = -eg;
     for (uint32_t ntask = 0;; ++ntask) {
         if (P.slot_bits && ntask) break;          // non-persistent launch: one task per wave
+        sq = tq;
         uint32_t base = 0;
         if (lane == 0) base = wv_atomic_add(P.counter, (uint32_t)(2 * GPW));
         base = wv_first(base);
         if (base >= P.n_cand) break;
-        // candidates of the two halves; an absent B repeats A (never written)
+        // candidates of the two halves; an absent B repeats A (never written), and
+        // an idle group fetches what queue slot `base` names and keeps xl = yl = 0
         bool valid[2];
         uint32_t cidx[2], sid[2] = {0, 0};
         int xl[2] = {0, 0}, yl[2] = {0, 0}, prow[2] = {NW16_NOROW, NW16_NOROW};
-        const uint8_t *Yp[2] = {P.q, P.q}, *Xg[2] = {P.db, P.db};
+        // The launch's arrays as wave-uniform values, said once per task: P lives in
+        // memory (nw_finish takes it by reference), so a field read where it is
+        // used is a load of its own whose value the compiler must take for
+        // divergent -- a branch on it predicates the loads behind it.
+        const uint8_t *const Pq = wv_first_ptr(P.q), *const Pdb = wv_first_ptr(P.db);
+        const uint64_t *const Pqs = wv_first_ptr(P.q_start), *const Pdbs = wv_first_ptr(P.db_start);
+        const uint32_t *const Pperm = wv_first_ptr(P.perm), *const Pread = wv_first_ptr(P.cand_read),
+                       *const Psid = wv_first_ptr(P.cand_sid);
+        const int32_t *const Prow = wv_first_ptr(P.cand_row);
+        // the per-half read and record pointers are two named values each (an array
+        // indexed by a run-time h lives in scratch, and every load through it is a flat one)
+        const uint8_t *Yp0, *Yp1, *Xg0, *Xg1;
+#pragma unroll
         for (int h = 0; h < 2; ++h) {
             cidx[h] = base + 2 * g + h;                                   // queue slot
             valid[h] = in_group && cidx[h] < P.n_cand;
         }
-        for (int h = 0; h < 2; ++h) {
-            const uint32_t w = valid[h] ? cidx[h] : cidx[0];
-            if (valid[0]) {
-                const uint32_t c = P.perm ? P.perm[w] : w;                // candidate
-                cidx[h] = c;
-                if (P.cand_row) prow[h] = P.cand_row[c];
-                const uint32_t rd = P.cand_read[c];
-                sid[h] = P.cand_sid[c];
-                const uint64_t xo = P.db_start[sid[h]];
-                xl[h] = (int)(P.db_start[sid[h] + 1] - xo);
-                Xg[h] = P.db + xo;
-                const uint64_t yo = P.q_start[rd];
-                Yp[h] = P.q + yo; yl[h] = (int)(P.q_start[rd + 1] - yo);
+        {
+            // The chain perm -> cand_* -> *_start, level by level: the loads of a
+            // level, both halves', are in flight together (three round trips).  No
+            // load is predicated: an idle group reads what queue slot `base` names
+            // (in range: base < n_cand) and drops it.
+            uint32_t c[2], rd[2], sd[2];
+            int pr[2] = {NW16_NOROW, NW16_NOROW};
+            uint64_t xo[2], xe[2], yo[2], ye[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const uint32_t w = valid[h] ? cidx[h] : valid[0] ? cidx[0] : base;
+                c[h] = Pperm ? wv_gld_u32(Pperm + w) : w;               // candidate
             }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                if (Prow) pr[h] = (int)wv_gld_u32(Prow + c[h]);
+                rd[h] = wv_gld_u32(Pread + c[h]);
+                sd[h] = wv_gld_u32(Psid + c[h]);
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                xo[h] = wv_gld_u64(Pdbs + sd[h]); xe[h] = wv_gld_u64(Pdbs + sd[h] + 1);
+                yo[h] = wv_gld_u64(Pqs + rd[h]); ye[h] = wv_gld_u64(Pqs + rd[h] + 1);
+            }
+            if (valid[0]) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    cidx[h] = c[h]; prow[h] = pr[h]; sid[h] = sd[h];
+                    xl[h] = (int)(xe[h] - xo[h]); yl[h] = (int)(ye[h] - yo[h]);
+                }
+            }
+            // (an idle group keeps the pointers of what it fetched, with xl = yl = 0: P.q
+            // and P.db themselves may lie below the uploaded range of a query or
+            // database shard, and the clamped loads below read index 0 of a lane
+            // without a read)
+            Xg0 = Pdb + xo[0]; Xg1 = Pdb + xo[1];
+            Yp0 = Pq + yo[0]; Yp1 = Pq + yo[1];
         }
+        auto Xg = [&](const int h) { return h ? Xg1 : Xg0; };
+        auto Yp = [&](const int h) { return h ? Yp1 : Yp0; };
         const int xlp = max(xl[0], xl[1]);
         int xmax = valid[0] ? xlp : 0, xmin = valid[0] ? min(xl[0], xl[1]) : INT_MAX;
         for (int o = 32; o > 0; o >>= 1) {
@@ -475,17 +524,62 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
         // an idle group (no candidate) reads group 0's record, so its lockstep
         // garbage stays a bounded DP like everyone else's
         uint8_t *X8 = wsm + (size_t)(valid[0] ? g : 0) * P.xstride;
+        // traceback window of the first sweep: steps [tw0, tw1), both odd (the
+        // loops advance t by 2 from 1); rows [lo, hi] of every candidate's
+        // prediction take steps lo .. hi + G - 1
+        int tw0 = INT_MAX - 2, tw1 = INT_MAX - 2;    // none: every step before "the window"
+        if (TWO && P.cand_row) {
+            int lo = INT_MAX, hi = INT_MIN, none = 0;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                if (!valid[h]) continue;
+                if (prow[h] == NW16_NOROW) {
+                    // no prediction (a weak hit: random reads' e-value passes, whose
+                    // best cells mostly sit on the last row with short paths)
+                    if (P.win_bottom < 0) { none = 1; continue; }
+                    lo = min(lo, xl[h] - 1 - P.win_bottom);
+                    hi = max(hi, xl[h] - 1);
+                    continue;
+                }
+                lo = min(lo, prow[h] - P.win_up);
+                hi = max(hi, prow[h] + yl[h] - 1 + P.win_down);
+            }
+            for (int o = 32; o > 0; o >>= 1) {
+                lo = min(lo, wv_shfl_xor(lo, o));
+                hi = max(hi, wv_shfl_xor(hi, o));
+                none = max(none, wv_shfl_xor(none, o));
+            }
+            if (!none && lo <= hi) {
+                int a = max(lo, 1), b = min(hi, xmax) + G;
+                a -= (a & 1) ^ 1; b += (b & 1) ^ 1;
+                if (b > a && b - a <= NW16_WIN_MAX) { tw0 = a; tw1 = b; }
+            }
+            tw0 = (int)wv_first((uint32_t)tw0); tw1 = (int)wv_first((uint32_t)tw1);   // wave-uniform (SGPRs)
+        }
+        smark(0);
         // the stop: only a wave whose every candidate is predicted (a weak
         // hit's best cell mostly sits on the last row, below bmin) and long
         // enough to hold a 12-mer
         bool can_stop = false;
         if (stopf) {
             bool scan[2], bad = false;
+#pragma unroll
             for (int h = 0; h < 2; ++h) {
                 scan[h] = valid[h] && prow[h] != NW16_NOROW && yl[h] >= NW16_STOP_MER;
                 bad = bad || (valid[h] && !scan[h]);
             }
             can_stop = !wv_any(bad) && wv_any(scan[0]);
+#if NW16_SKIP_NOSTOP
+            // The stop is tested at checkpoint steps t = 1 + m CK (m >= 1) with a
+            // pair of steps still to run, t + 1 <= tend - 1, and never inside or
+            // before the window, t >= tw1 (stop_now below): a wave without such a
+            // step -- its window ends at the record's bottom -- cannot stop, and
+            // is spared the table and the scan.
+            {
+                const int tlast = 1 + CK * ((xmax - 1 + G - 3) / CK);     // the last checkpoint step that is tested
+                if (xmax - 1 + G - 3 < CK || (tw1 > tw0 && tlast < tw1)) can_stop = false;
+            }
+#endif
             if (can_stop) {
                 constexpr uint32_t EMPTY = 0xFFFFFFFFu, CMASK = (1u << (2 * NW16_STOP_MER)) - 1u;
                 const uint32_t ns = (uint32_t)stop_slots;
@@ -494,16 +588,41 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
                 auto bucket_of = [&](const uint32_t code) { return (((code * 0x9E3779B1u) >> 16) * nb) >> 16; };
                 if (valid[0])
                     for (uint32_t k = (uint32_t)gl; k < 2 * ns; k += (uint32_t)G) tab[k] = EMPTY;
-                wv_lds_sync();
+                // A contiguous share of the read's 12-mers per lane: `per` <= K of
+                // them (nk < G * K), so K + 11 bases, fetched as TQ dwords -- both
+                // halves' before the first use -- and kept as 2-bit codes in one
+                // 64-bit value, base b of the share at bits 2 (4 TQ - 1 - b): the
+                // inserts run from registers.  A dword that would pass the read's
+                // end is read at its last four bytes and shifted (yl >= 12 here; a
+                // lane of an idle group, yl = 0, reads the first bytes of the read it
+                // fetched and dropped, queue slot `base`'s, which has 12 too).
+                constexpr int TQ = (K + NW16_STOP_MER - 1 + 3) / 4;
+                static_assert(4 * TQ <= 32, "the share's codes fit 64 bits");
+                uint64_t ybits[2];
+                int ycnt[2];
+#pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    if (!scan[h]) continue;
-                    // a contiguous share of the read's 12-mers per lane, one rolling code
                     const int nk = yl[h] - (NW16_STOP_MER - 1), per = (nk + G - 1) / G;
                     const int k0 = gl * per, k1 = min(nk, k0 + per);
-                    uint32_t code = 0;
-                    for (int b = k0; b < k1 + NW16_STOP_MER - 1; ++b) {
-                        code = ((code << 2) | base_code(Yp[h][b])) & CMASK;
-                        if (b < k0 + NW16_STOP_MER - 1) continue;
+                    ycnt[h] = scan[h] ? max(k1 - k0, 0) : 0;
+                    uint32_t w[TQ];
+#pragma unroll
+                    for (int q = 0; q < TQ; ++q) {
+                        const int pos = k0 + 4 * q, st = max(min(pos, yl[h] - 4), 0), sh = pos - st;
+                        const uint32_t v = wv_gld_u32(Yp(h) + st);
+                        w[q] = sh >= 4 ? 0u : v >> (8 * sh);
+                    }
+                    uint64_t bits = 0;
+#pragma unroll
+                    for (int q = 0; q < TQ; ++q)      // four codes c0 .. c3 of a dword -> c0 << 6 | c1 << 4 | c2 << 2 | c3
+                        bits = (bits << 8) | ((((w[q] >> 1) & 0x03030303u) * 0x40100401u) >> 24);
+                    ybits[h] = bits;
+                }
+                wv_lds_sync();
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    for (int b = 0; b < ycnt[h]; ++b) {
+                        const uint32_t code = (uint32_t)(ybits[h] >> (2 * (4 * TQ - NW16_STOP_MER - b))) & CMASK;
                         // the first free slot from the home bucket's first on: every slot
                         // before it is taken for good, so a probe that walks the buckets
                         // from the home one meets the code before it meets a free slot
@@ -515,6 +634,7 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
                     }
                 }
                 wv_lds_sync();
+                smark(1);
                 // the record's rows from the bottom up, G * 32 per block, 32 per lane,
                 // of which every NW16_STOP_STRIDE-th is probed; row i holds a 12-mer
                 // if i <= xlen - 12, and `top` (a multiple of the stride, like every
@@ -538,14 +658,14 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
                         const bool on = act[h] && r0[h] + LROWS > 0;
                         uint32_t w[LBYTES / 4] = {};
                         if (on && r0[h] >= 0) {                       // (r0 + LBYTES <= xlen: the last probed 12-mer ends there)
-                            __builtin_memcpy(w, Xg[h] + r0[h], LBYTES);
+                            __builtin_memcpy(w, Xg(h) + r0[h], LBYTES);
                         } else if (on) {
 #pragma unroll
                             for (int q = 0; q < LBYTES / 4; ++q) {
                                 uint32_t v = 0;
 #pragma unroll
                                 for (int b = 0; b < 4; ++b)
-                                    v |= (uint32_t)Xg[h][min(max(r0[h] + 4 * q + b, 0), xl[h] - 1)] << (8 * b);
+                                    v |= (uint32_t)Xg(h)[min(max(r0[h] + 4 * q + b, 0), xl[h] - 1)] << (8 * b);
                                 w[q] = v;
                             }
                         }
@@ -594,6 +714,7 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
                 }
                 // the lane's two free slots of each half (until the reduction): the
                 // row formula's constant part and bmin, read back at checkpoints
+#pragma unroll
                 for (int h = 0; h < 2; ++h) {
 #ifdef IMSAME_WAVE_EMU
                     const int bm = !scan[h] ? INT_MAX : P.bmin ? P.bmin[yl[h]] : nw16_bmin(yl[h], ig, eg);
@@ -604,6 +725,7 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
                     red[lane * 8 + 4 * h + 3] = bm;
                 }
                 wv_lds_sync();                    // the tables are read: the record may take their place
+                smark(2);
             }
         }
         if (valid[0]) {
@@ -618,19 +740,16 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
             for (int c = gl; c < nch; c += G) {
                 const int k0 = c << 4;
                 uint32_t w[2][4];
+#pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     if (k0 + 16 <= xl[h]) {
-                        __builtin_memcpy(w[h], Xg[h] + k0, 16);
-                    } else if (k0 >= xl[h]) {
-                        const uint32_t v = (uint32_t)Xg[h][xl[h] - 1] * 0x01010101u;
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) w[h][q] = v;
+                        wv_gld_16(Xg(h) + k0, w[h]);
                     } else {
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
                             uint32_t v = 0;
 #pragma unroll
-                            for (int b = 0; b < 4; ++b) v |= (uint32_t)Xg[h][min(k0 + 4 * q + b, xl[h] - 1)] << (8 * b);
+                            for (int b = 0; b < 4; ++b) v |= wv_gld_u8(Xg(h) + min(k0 + 4 * q + b, xl[h] - 1)) << (8 * b);
                             w[h][q] = v;
                         }
                     }
@@ -644,38 +763,8 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
             }
         }
         wv_lds_sync();
+        smark(3);
 
-        // traceback window of the first sweep: steps [tw0, tw1), both odd (the
-        // loops advance t by 2 from 1); rows [lo, hi] of every candidate's
-        // prediction take steps lo .. hi + G - 1
-        int tw0 = INT_MAX - 2, tw1 = INT_MAX - 2;    // none: every step before "the window"
-        if (TWO && P.cand_row) {
-            int lo = INT_MAX, hi = INT_MIN, none = 0;
-            for (int h = 0; h < 2; ++h) {
-                if (!valid[h]) continue;
-                if (prow[h] == NW16_NOROW) {
-                    // no prediction (a weak hit: random reads' e-value passes, whose
-                    // best cells mostly sit on the last row with short paths)
-                    if (P.win_bottom < 0) { none = 1; continue; }
-                    lo = min(lo, xl[h] - 1 - P.win_bottom);
-                    hi = max(hi, xl[h] - 1);
-                    continue;
-                }
-                lo = min(lo, prow[h] - P.win_up);
-                hi = max(hi, prow[h] + yl[h] - 1 + P.win_down);
-            }
-            for (int o = 32; o > 0; o >>= 1) {
-                lo = min(lo, wv_shfl_xor(lo, o));
-                hi = max(hi, wv_shfl_xor(hi, o));
-                none = max(none, wv_shfl_xor(none, o));
-            }
-            if (!none && lo <= hi) {
-                int a = max(lo, 1), b = min(hi, xmax) + G;
-                a -= (a & 1) ^ 1; b += (b & 1) ^ 1;
-                if (b > a && b - a <= NW16_WIN_MAX) { tw0 = a; tw1 = b; }
-            }
-            tw0 = (int)wv_first((uint32_t)tw0); tw1 = (int)wv_first((uint32_t)tw1);   // wave-uniform (SGPRs)
-        }
         const int tb0 = TWO ? tw0 : 0;             // step of traceback record 0
 
         // ------------------------------------------------------------ sweep
@@ -685,15 +774,27 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
         const uint32_t NBIG = pk1(-NW16_BIG) ^ NW16_H, EGN = pk1(-eg), IGEN = pk1(-(ig + eg));   // biased; gap magnitudes
         uint32_t yreg[K], lastm[K];
         bool ownC[2], lact[2];
+#pragma unroll
         for (int h = 0; h < 2; ++h) {
             ownC[h] = valid[0] && yl[h] >= 2 && yl[h] - 1 >= j0 && yl[h] - 1 < j0 + K;
             lact[h] = valid[0] && j0 < yl[h];
         }
+        // The read's bases of columns j0 - 1 .. j0 + K - 1, both halves: byte loads
+        // at clamped indices, none predicated, so all 2 (K + 1) are in flight
+        // together; the codes are picked from registers.  Byte loads, 40 of them at 19
+        // columns: one round trip either way, and dword loads (clamped starts and a
+        // shift per dword, as the stop's table does) were not tried.  (A lane of an idle group,
+        // yl = 0, reads the first byte of the read it fetched and uses nothing of it.)
+        uint32_t ybyte[2][K + 1];
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int s = 0; s <= K; ++s) ybyte[h][s] = wv_gld_u8(Yp(h) + max(min(j0 - 1 + s, yl[h] - 1), 0));
 #pragma unroll
         for (int s = 0; s < K; ++s) {
             const int j = j0 + s;
-            const uint32_t ya = (valid[0] && j >= 0 && j < yl[0]) ? base_code(Yp[0][j]) : 0u;
-            const uint32_t yb = (valid[0] && j >= 0 && j < yl[1]) ? base_code(Yp[1][j]) : 0u;
+            const uint32_t ya = (valid[0] && j >= 0 && j < yl[0]) ? base_code((uint8_t)ybyte[0][s + 1]) : 0u;
+            const uint32_t yb = (valid[0] && j >= 0 && j < yl[1]) ? base_code((uint8_t)ybyte[1][s + 1]) : 0u;
             yreg[s] = nw16_ycol(ya, yb);
             lastm[s] = ((ownC[0] && yl[0] - 1 - j0 == s) ? 0x0000FFFFu : 0u) |
                        ((ownC[1] && yl[1] - 1 - j0 == s) ? 0xFFFF0000u : 0u);
@@ -703,7 +804,7 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
         const Nw16Row xr0 = nw16_row(xrow);
         uint32_t yprev = nw16_ycol(0u, 0u);
         if (valid[0] && j0 > 0) {
-            const uint32_t ya = base_code(Yp[0][min(j0 - 1, yl[0] - 1)]), yb = base_code(Yp[1][min(j0 - 1, yl[1] - 1)]);
+            const uint32_t ya = base_code((uint8_t)ybyte[0][0]), yb = base_code((uint8_t)ybyte[1][0]);   // column min(j0, yl) - 1
             yprev = nw16_ycol(ya, yb);
         }
         const uint32_t t0prev = nw16_sc_biased(nw16_sc(xr0, yprev));
@@ -864,6 +965,7 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
         };
         auto ck = [&](const int t) { if (TWO && t == nextck) { save(mck); ++mck; nextck += CK; } };
         if (TWO) save(0);
+        smark(4);
         mark(0);
         // (cur, own) and (in0, in1) swap every step; every loop advances t by 2
         // from 1, so the phase carries over and, in two-pass mode, a pair lies
@@ -966,7 +1068,7 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
         mark(2);
         if (!TWO) {
             for (int h = 0; h < 2; ++h) {
-                const TbAcc16<K, OFF> acc16 = {tbw, X8, Yp[h], gg, G, h, 0};
+                const TbAcc16<K, OFF> acc16 = {tbw, X8, Yp(h), gg, G, h, 0};
                 nw_finish(P, acc16, xl[h], yl[h], valid[h], gg, gl, G, bscore[h], bx[h], by[h], cidx[h], sid[h]);
             }
             wv_lds_sync();
@@ -985,7 +1087,7 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
             for (int h = 0; h < 2; ++h) cov[h] = todo[h] && bx[h] + G <= tw1;
             if (wv_any(cov[0] || cov[1])) {
                 for (int h = 0; h < 2; ++h) {
-                    TbAcc16<K, OFF> acc16 = {tbw, X8, Yp[h], gg, G, h, tw0};
+                    TbAcc16<K, OFF> acc16 = {tbw, X8, Yp(h), gg, G, h, tw0};
                     acc16.t1 = tw1;
                     const bool lost = nw_finish(P, acc16, xl[h], yl[h], cov[h], gg, gl, G, bscore[h], bx[h], by[h],
                                                 cidx[h], sid[h]);
@@ -1059,7 +1161,7 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
             {   // restore: half A from its checkpoint, half B from its own
                 const uint32_t *pa = ckw + (uint32_t)((t0h[0] - 1) / CK) * (NST * 64u);
                 const uint32_t *pb = ckw + (uint32_t)((t0h[1] - 1) / CK) * (NST * 64u);
-                auto ld = [&](const int r) { return wv_bfi(0x0000FFFFu, pa[r * 64], pb[r * 64]); };
+                auto ld = [&](const int r) { return wv_bfi(0x0000FFFFu, wv_gld_u32(pa + r * 64), wv_gld_u32(pb + r * 64)); };
 #pragma unroll
                 for (int s = 0; s < K; ++s) {
                     A[s] = ld(s); B[s] = ld(K + s);
@@ -1089,7 +1191,7 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
             wv_mem_sync();                        // band traceback written by all lanes, read by the walkers
             mark(3);
             for (int h = 0; h < 2; ++h) {
-                const TbAcc16<K, OFF> acc16 = {tbw, X8, Yp[h], gg, G, h, t0h[h]};
+                const TbAcc16<K, OFF> acc16 = {tbw, X8, Yp(h), gg, G, h, t0h[h]};
                 todo[h] = nw_finish(P, acc16, xl[h], yl[h], todo[h], gg, gl, G, bscore[h], bx[h], by[h], cidx[h],
                                     sid[h]);
             }
@@ -1103,6 +1205,7 @@ __device__ __forceinline__ void nw16_wave(const NwLaunch &P, uint8_t *wsm, const
     if (P.prof && lane == 0) {
         for (int k = 0; k < 5; ++k) wv_atomic_add64(P.prof + k, ph[k]);
         wv_atomic_add64(P.prof + 5, wv_realtime() - rt0);
+        for (int k = 0; k < 5; ++k) wv_atomic_add64(P.prof + 16 + k, sp[k]);
     }
 }
 

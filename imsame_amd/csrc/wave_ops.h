@@ -34,6 +34,12 @@ WV_DEVICE bool wv_any(bool p) { return __any(p); }
 WV_DEVICE int wv_shfl(int v, int src) { return __shfl(v, src); }
 WV_DEVICE int wv_shfl_xor(int v, int m) { return __shfl_xor(v, m); }
 WV_DEVICE uint32_t wv_first(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+// a pointer every lane holds alike, as a wave-uniform value (a scalar register pair)
+template <typename T>
+WV_DEVICE T *wv_first_ptr(T *p) {
+    const uint64_t v = (uint64_t)p;
+    return (T *)((uint64_t)wv_first((uint32_t)v) | ((uint64_t)wv_first((uint32_t)(v >> 32)) << 32));
+}
 // lane l's v (wave-uniform; every lane must be active)
 WV_DEVICE int wv_readlane(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
 WV_DEVICE uint32_t wv_atomic_add(uint32_t *p, uint32_t v) { return atomicAdd(p, v); }
@@ -107,6 +113,20 @@ WV_DEVICE uint32_t wv_perm(uint32_t hi, uint32_t lo, uint32_t sel) { return __bu
 // the 32 bits of {hi:lo} from bit s up (s < 32): one v_alignbit_b32
 WV_DEVICE uint32_t wv_alignbit(uint32_t hi, uint32_t lo, uint32_t s) { return __builtin_amdgcn_alignbit(hi, lo, s); }
 WV_DEVICE uint32_t wv_bitrev(uint32_t v) { return __builtin_bitreverse32(v); }        // v_bfrev_b32
+// Loads through the GLOBAL address space (global_load_*, where a pointer the
+// compiler cannot trace gives flat_*, which counts against the LDS counter
+// too): p points to device memory, never to LDS or scratch.  Any alignment.
+#define WV_GLOBAL __attribute__((address_space(1)))
+typedef uint32_t wv_u32_u __attribute__((aligned(1)));
+typedef uint32_t wv_v4 __attribute__((ext_vector_type(4)));
+typedef wv_v4 wv_v4_u __attribute__((aligned(1)));
+WV_DEVICE uint32_t wv_gld_u8(const uint8_t *p) { return *(const WV_GLOBAL uint8_t *)p; }
+WV_DEVICE uint32_t wv_gld_u32(const void *p) { return *(const WV_GLOBAL wv_u32_u *)p; }
+WV_DEVICE uint64_t wv_gld_u64(const uint64_t *p) { return *(const WV_GLOBAL uint64_t *)p; }
+WV_DEVICE void wv_gld_16(const void *p, uint32_t (&w)[4]) {
+    const wv_v4 v = *(const WV_GLOBAL wv_v4_u *)p;
+    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+}
 // (w << 1) | c in one v_addc_co_u32 (w + w + carry): the compare's lane mask
 // is the carry-in
 WV_DEVICE uint32_t wv_shift_in(uint32_t w, bool c) {
@@ -195,6 +215,11 @@ inline int wv_shfl(int v, int src) {
 inline int wv_shfl_xor(int v, int m) { return wv_shfl(v, wvemu::t_lane ^ m); }
 inline uint32_t wv_first(uint32_t v) { return (uint32_t)wv_shfl((int)v, 0); }
 inline int wv_readlane(int v, int l) { return wv_shfl(v, l); }
+template <typename T>
+inline T *wv_first_ptr(T *p) {
+    const uint64_t v = (uint64_t)p;
+    return (T *)((uint64_t)wv_first((uint32_t)v) | ((uint64_t)wv_first((uint32_t)(v >> 32)) << 32));
+}
 inline uint32_t wv_atomic_add(uint32_t *p, uint32_t v) {
     return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST);
 }
@@ -229,6 +254,10 @@ inline uint32_t pk_minu(uint32_t a, uint32_t b) {
     return lo | (hi << 16);
 }
 inline uint32_t pk_neg_mask(uint32_t a) { return pk_map(a, 0, [](int x, int) { return x < 0 ? -1 : 0; }); }
+inline uint32_t wv_gld_u8(const uint8_t *p) { return *p; }
+inline uint32_t wv_gld_u32(const void *p) { uint32_t v; memcpy(&v, p, 4); return v; }
+inline uint64_t wv_gld_u64(const uint64_t *p) { return *p; }
+inline void wv_gld_16(const void *p, uint32_t (&w)[4]) { memcpy(w, p, 16); }
 inline uint32_t wv_shift_in(uint32_t w, bool c) { return (w << 1) | (c ? 1u : 0u); }
 inline uint32_t wv_and_or(uint32_t m, uint32_t c, uint32_t w) { return (m & c) | w; }
 inline uint32_t wv_bfi(uint32_t m, uint32_t a, uint32_t b) { return (m & a) | (~m & b); }
