@@ -1123,10 +1123,57 @@ static void timeline_print(const std::vector<imsame_ctx *> &L) {
     }
 }
 
+// Every NW entry point, once.  A row's key is its family, then -- packed and
+// mid -- the columns per lane, LAST and TWO, or -- int32 -- multi-strip.
+// nw_kernel_row finds a plan's row: plan_nw asks its occupancy, launch_nw
+// launches it and names it, nw16_np_part_cu sizes the slot partitions over the
+// packed and mid rows.  A new form is one row here plus its rule in plan_nw.
+using NwKernelFn = void (*)(NwLaunch);
+enum NwFamily { NWF_INT32, NWF_NWL, NWF_NWP, NWF_PACKED, NWF_MID };
+struct NwKernelRow { NwFamily fam; int k; bool last, two, multi; NwKernelFn fn; const char *name; };
+static const NwKernelRow NW_KERNELS[] = {
+    {NWF_PACKED, NW16_K, false, true, false, nw16_kernel<NW16_K, false, true>, "nw16_kernel<10,two>"},
+    {NWF_PACKED, NW16_K, true, true, false, nw16_kernel<NW16_K, true, true>, "nw16_kernel<10,last,two>"},
+    {NWF_PACKED, NW16_K, false, false, false, nw16_kernel<NW16_K, false, false>, "nw16_kernel<10,one>"},
+    {NWF_PACKED, NW16_K, true, false, false, nw16_kernel<NW16_K, true, false>, "nw16_kernel<10,last,one>"},
+    {NWF_PACKED, NW16_K5, false, true, false, nw16_kernel<NW16_K5, false, true>, "nw16_kernel<5,two>"},
+    {NWF_PACKED, NW16_K5, true, true, false, nw16_kernel<NW16_K5, true, true>, "nw16_kernel<5,last,two>"},
+    {NWF_PACKED, NW16_K5, false, false, false, nw16_kernel<NW16_K5, false, false>, "nw16_kernel<5,one>"},
+    {NWF_PACKED, NW16_K5, true, false, false, nw16_kernel<NW16_K5, true, false>, "nw16_kernel<5,last,one>"},
+    // 19 columns: 150 = 8 x 19 - OFF puts the last column in slot K-1, always LAST
+    {NWF_PACKED, NW16_K19, true, true, false, nw16_kernel<NW16_K19, true, true, NW16_K19_OFF>, "nw16_kernel<19,last,two>"},
+    {NWF_PACKED, NW16_K19, true, false, false, nw16_kernel<NW16_K19, true, false, NW16_K19_OFF>, "nw16_kernel<19,last,one>"},
+    {NWF_PACKED, NW16_K3, false, true, false, nw16_kernel<NW16_K3, false, true>, "nw16_kernel<3,two>"},
+    {NWF_PACKED, NW16_K3, true, true, false, nw16_kernel<NW16_K3, true, true>, "nw16_kernel<3,last,two>"},
+    {NWF_PACKED, NW16_K3, false, false, false, nw16_kernel<NW16_K3, false, false>, "nw16_kernel<3,one>"},
+    {NWF_PACKED, NW16_K3, true, false, false, nw16_kernel<NW16_K3, true, false>, "nw16_kernel<3,last,one>"},
+    {NWF_MID, NW16_K, false, true, false, nw16_mid_kernel<false, true>, "nw16_mid_kernel<two>"},
+    {NWF_MID, NW16_K, true, true, false, nw16_mid_kernel<true, true>, "nw16_mid_kernel<last,two>"},
+    {NWF_MID, NW16_K, false, false, false, nw16_mid_kernel<false, false>, "nw16_mid_kernel<one>"},
+    {NWF_MID, NW16_K, true, false, false, nw16_mid_kernel<true, false>, "nw16_mid_kernel<last,one>"},
+    {NWF_NWP, 0, false, false, false, nwp_kernel, "nwp_kernel"},
+    {NWF_NWL, 0, false, false, false, nwl_kernel, "nwl_kernel"},
+    {NWF_INT32, 0, false, false, true, nw_kernel<true>, "nw_kernel<multi>"},
+    {NWF_INT32, 0, false, false, false, nw_kernel<false>, "nw_kernel<single>"},
+};
+
 struct NwPlan { int G, GPW, xcap, xstride, steps, nstr, k; bool pk, last4, two, lng, lp, np; size_t lds; unsigned blocks, max_blocks;
                 bool mid;              // pk: the 10-column form of reads of 161 .. NW16_YMAX bases (nw16_mid_kernel)
                 uint32_t slot_words;   // np: bitmap words per XCD partition (arena slots = 8 x 32 x slot_words)
-                uint64_t tb_dw, ck_dw, bnd_dw; int band_w; };
+                uint64_t tb_dw, ck_dw, bnd_dw; int band_w;
+                const NwKernelRow *row; };      // the kernel the plan runs (nw_kernel_row)
+
+// The row of a finished plan; none (nullptr) is a plan no kernel was built
+// for: the caller fails with IMSAME_E_STATE, it never runs another kernel.
+// (Off the packed forms k, last4 and two are 0, as in their rows.)
+static const NwKernelRow *nw_kernel_row(const NwPlan &pl) {
+    const NwFamily fam = pl.lp ? NWF_NWP : pl.lng ? NWF_NWL : pl.mid ? NWF_MID : pl.pk ? NWF_PACKED : NWF_INT32;
+    for (const NwKernelRow &r : NW_KERNELS)
+        if (r.fam == fam && r.k == pl.k && r.last == pl.last4 && r.two == pl.two &&
+            r.multi == (fam == NWF_INT32 && pl.nstr > 1))
+            return &r;
+    return nullptr;
+}
 
 // Long reads take the two-pass nwl_kernel (nwl_kernel.hip) unless the int32
 // kernel is forced (IMSAME_FLAG_NW32, or IMSAME_NWL=0 for A/B runs).
@@ -1190,23 +1237,24 @@ static int nw16_np_part_cu(imsame_ctx *c) {
     if (c->np_part_cu >= 0) return c->np_part_cu;
     int m = 0;
     bool ok = true;
-    auto q = [&](const void *f) {
+    for (const NwKernelRow &r : NW_KERNELS) {
+        if (r.fam != NWF_PACKED && r.fam != NWF_MID) continue;
         int a = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, f, 256, 0) != hipSuccess || a < 1) ok = false;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, r.fn, 256, 0) != hipSuccess || a < 1) ok = false;
         m = std::max(m, a);
-    };
-    q((const void *)nw16_kernel<NW16_K, false, true>);  q((const void *)nw16_kernel<NW16_K, true, true>);
-    q((const void *)nw16_kernel<NW16_K, false, false>); q((const void *)nw16_kernel<NW16_K, true, false>);
-    q((const void *)nw16_kernel<NW16_K5, false, true>); q((const void *)nw16_kernel<NW16_K5, true, true>);
-    q((const void *)nw16_kernel<NW16_K5, false, false>); q((const void *)nw16_kernel<NW16_K5, true, false>);
-    q((const void *)nw16_kernel<NW16_K19, true, true, NW16_K19_OFF>);
-    q((const void *)nw16_kernel<NW16_K19, true, false, NW16_K19_OFF>);
-    q((const void *)nw16_kernel<NW16_K3, false, true>); q((const void *)nw16_kernel<NW16_K3, true, true>);
-    q((const void *)nw16_kernel<NW16_K3, false, false>); q((const void *)nw16_kernel<NW16_K3, true, false>);
-    q((const void *)nw16_mid_kernel<false, true>);  q((const void *)nw16_mid_kernel<true, true>);
-    q((const void *)nw16_mid_kernel<false, false>); q((const void *)nw16_mid_kernel<true, false>);
+    }
     c->np_part_cu = ok ? m : 0;
     return c->np_part_cu;
+}
+// Bitmap words of one XCD partition holding part_cu blocks (of 4 waves) per CU
+// of its ncu / 8 CUs: the arena has 8 x 32 x np_slot_words slots.
+static uint32_t np_slot_words(const imsame_ctx *c, int part_cu) {
+    return (uint32_t)((((uint64_t)c->ncu / 8) * part_cu * 4 + 31) / 32);
+}
+// both launches number the arena's slots the same way: they may run at once
+static bool np_same_layout(const NwPlan &a, const NwPlan &b) {
+    return a.np && b.np && b.slot_words == a.slot_words && b.tb_dw == a.tb_dw && b.ck_dw == a.ck_dw &&
+           b.bnd_dw == a.bnd_dw && b.max_blocks == a.max_blocks;
 }
 
 // Columns per lane of a packed launch.  A launch is a queue of tasks (8
@@ -1341,30 +1389,12 @@ static int plan_nw(imsame_ctx *c, uint32_t ymax, uint32_t xcap, uint32_t ncand, 
     pl->bnd_dw = pl->lp ? nwp_seam_words(sh, ymax) : pl->lng ? nwl_seam_words(sh) : 3ull * pl->xcap;
     pl->lds = (size_t)wpb * (pl->pk ? nw16_wave_lds(pl->GPW, pl->xstride)
                              : pl->lng ? nwl_wave_lds(pl->xstride) : nw_wave_lds(pl->GPW, pl->xstride));
+    // the occupancy of the kernel the launch runs (LAST siblings allocate the
+    // same registers and no static LDS: profiles/nw_kernel_table/bench.md)
+    if (!(pl->row = nw_kernel_row(*pl))) return IMSAME_E_STATE;
     int per_cu = 0;
-    const bool k5 = pl->k == NW16_K5, k19 = pl->k == NW16_K19, k3 = pl->k == NW16_K3;
-    hipError_t oe = pl->lp ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nwp_kernel, wpb * 64, pl->lds)
-                  : pl->lng ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nwl_kernel, wpb * 64, pl->lds)
-                  : pl->mid ? (pl->two ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nw16_mid_kernel<false, true>,
-                                                                                  wpb * 64, pl->lds)
-                                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nw16_mid_kernel<false, false>,
-                                                                                  wpb * 64, pl->lds))
-                  : k3 ? (pl->two ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nw16_kernel<NW16_K3, false, true>,
-                                                                             wpb * 64, pl->lds)
-                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nw16_kernel<NW16_K3, false, false>,
-                                                                             wpb * 64, pl->lds))
-                  : k19 ? (pl->two ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                                         &per_cu, nw16_kernel<NW16_K19, true, true, NW16_K19_OFF>, wpb * 64, pl->lds)
-                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                                         &per_cu, nw16_kernel<NW16_K19, true, false, NW16_K19_OFF>, wpb * 64, pl->lds))
-                  : pl->two ? (k5 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nw16_kernel<NW16_K5, false, true>, wpb * 64, pl->lds)
-                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nw16_kernel<NW16_K, false, true>, wpb * 64, pl->lds))
-                  : pl->pk ? (k5 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nw16_kernel<NW16_K5, false, false>, wpb * 64, pl->lds)
-                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nw16_kernel<NW16_K, false, false>, wpb * 64, pl->lds))
-                  : (pl->nstr > 1)
-                      ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nw_kernel<true>, wpb * 64, pl->lds)
-                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nw_kernel<false>, wpb * 64, pl->lds);
-    if (oe != hipSuccess || per_cu < 1) per_cu = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pl->row->fn, wpb * 64, pl->lds) != hipSuccess || per_cu < 1)
+        per_cu = 1;
     // Non-persistent packed launches (one wave per task, arena slots from a
     // per-XCD free bitmap): waves leave as their tasks end, so other lanes'
     // seed scans and small kernels get wave slots during a long launch
@@ -1382,7 +1412,7 @@ static int plan_nw(imsame_ctx *c, uint32_t ymax, uint32_t xcap, uint32_t ncand, 
         const imsame_ctx *ao = c->np_owner ? c->np_owner : c;
         uint64_t tb_dw = 0, ck_dw = 0;
         np_strides(xcap, ao->np_mid, &tb_dw, &ck_dw);       // the call's layout (align_impl)
-        const uint32_t words = (uint32_t)((((uint64_t)c->ncu / 8) * part_cu * wpb + 31) / 32);
+        const uint32_t words = np_slot_words(c, part_cu);
         const uint64_t ns = (uint64_t)8 * 32 * words;
         // the arena np_prepare actually holds (it skips the allocation when
         // free HBM is short, e.g. after a long-read call grew c->tb): a plan
@@ -1398,7 +1428,7 @@ static int plan_nw(imsame_ctx *c, uint32_t ymax, uint32_t xcap, uint32_t ncand, 
     if (!pl->np) { per_cu = std::min(per_cu, 8); part_cu = per_cu; }
     const uint32_t cpw = (pl->pk || pl->lp) ? 2 * pl->GPW : pl->GPW;    // candidates per wave pull
     const uint64_t waves_needed = (ncand + cpw - 1) / cpw;
-    pl->slot_words = (uint32_t)((((uint64_t)c->ncu / 8) * part_cu * wpb + 31) / 32);
+    pl->slot_words = np_slot_words(c, part_cu);
     pl->blocks = (unsigned)std::max<uint64_t>(1, pl->np ? (waves_needed + wpb - 1) / wpb
                                                          : std::min<uint64_t>((uint64_t)c->ncu * per_cu, (waves_needed + wpb - 1) / wpb));
     // Traceback arena: one slot per resident wave.  Long reads against long
@@ -1464,7 +1494,7 @@ static int np_prepare(imsame_ctx *o, uint32_t xcap) {
     // test hook: behave as if free HBM could not hold the arena (the state a
     // long-read call that grew the persistent arena leaves behind)
     if (const char *sk = getenv("IMSAME_DEBUG_NP_SKIP")) if (atoi(sk)) return 0;
-    const uint32_t words = (uint32_t)((((uint64_t)o->ncu / 8) * nw16_np_part_cu(o) * 4 + 31) / 32);
+    const uint32_t words = np_slot_words(o, nw16_np_part_cu(o));
     const uint64_t ns = (uint64_t)8 * 32 * words, nbits = (uint64_t)8 * words * 4;
     uint64_t tb_dw = 0, ck_dw = 0;
     np_strides(xcap < 2 ? 2 : xcap, o->np_mid, &tb_dw, &ck_dw);
@@ -1488,35 +1518,55 @@ static int np_prepare(imsame_ctx *o, uint32_t xcap) {
     return 0;
 }
 
-// Queue order of a launch's candidates by predicted first row (8-row
-// buckets, unpredicted first: launch_nw's own ordering, done ahead of it) into
-// the cperm buffer of queue qi, and the number of unpredicted candidates --
-// the first *nweak entries -- read back (the stream is synchronized).
-static int row_perm(imsame_ctx *c, const int32_t *crow, uint32_t n, uint32_t xcap_pl, int qi, uint32_t *nweak) {
+// Queue order of a launch's candidates by predicted first row (8-row buckets
+// of the plan's xcap_pl + 512 rows, unpredicted first), enqueued on queue qi's
+// stream into its cperm buffer: *perm.  The bucket counts stay in its rhist
+// buffer, the unpredicted candidates' first.
+static int row_order(imsame_ctx *c, const int32_t *crow, uint32_t n, uint32_t xcap_pl, int qi, const uint32_t **perm) {
     hipStream_t s = qi ? c->stream_b : c->stream;
-    const uint32_t nb = xcap_pl / 8 + 512 / 8 + 2;
+    const uint32_t nb = (xcap_pl + 512) / 8 + 2;
     DBuf &cperm = qi ? c->cperm_b : c->cperm, &rhist = qi ? c->rhist_b : c->rhist;
     if (cperm.ensure((uint64_t)n * 4) || rhist.ensure((uint64_t)nb * 8)) return IMSAME_E_OOM;
     uint32_t *hist = rhist.as<uint32_t>(), *cur = hist + nb;
-    STALL(c, s);
     HIPCHK(hipMemsetAsync(hist, 0, (size_t)nb * 4, s));
     row_hist_kernel<<<std::min(nblk(n, 256), ROW_BLOCKS), 256, 0, s>>>(crow, n, nb, hist);
     row_scan_kernel<<<1, 1024, 0, s>>>(hist, nb, cur);
     row_scatter_kernel<<<std::min(nblk(n, 256), ROW_BLOCKS), 256, 0, s>>>(crow, n, nb, cur, cperm.as<uint32_t>());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(nweak, hist, 4, hipMemcpyDeviceToHost, s));
+    *perm = cperm.as<uint32_t>();
+    return 0;
+}
+
+// launch_nw's own ordering, done ahead of it: the order (row_order) and the
+// number of unpredicted candidates -- the first *nweak entries -- read back
+// (the stream is synchronized).
+static int row_perm(imsame_ctx *c, const int32_t *crow, uint32_t n, uint32_t xcap_pl, int qi, uint32_t *nweak) {
+    hipStream_t s = qi ? c->stream_b : c->stream;
+    const uint32_t *perm = nullptr;
+    STALL(c, s);
+    if (int rc = row_order(c, crow, n, xcap_pl, qi, &perm)) return rc;
+    HIPCHK(hipMemcpyAsync(nweak, (qi ? c->rhist_b : c->rhist).p, 4, hipMemcpyDeviceToHost, s));
     LANE_SYNC(c, s);
     return 0;
 }
 
-static int launch_nw(imsame_ctx *c, NwPlan &pl, const uint32_t *cread, const uint32_t *csid, uint32_t n,
-                     imsame_read_result *outp, int64_t ig, int64_t eg, const imsame_params *p, uint32_t ymax,
-                     uint32_t xmax, uint32_t *work, const uint8_t *dbp, const uint64_t *dbs, const uint8_t *qp,
-                     const uint64_t *qs, uint32_t paths_cap, double *ms, const int32_t *crow = nullptr, int qi = 0,
-                     bool wait = true, const uint32_t *perm_in = nullptr) {
-    // perm_in: the queue order is given (row_perm; the candidates are
-    // perm_in[0 .. n)), crow their predicted rows
-    // qi 1: round 1b's stream; wait false: enqueue only (nw_launch_done)
+// What the NW launches of one call share: its parameters (the gaps are p's),
+// the longest read and record cap its tables are built for, the records, the
+// reads and the room of the device path arena.
+struct NwCall { const imsame_params *p; uint32_t ymax, xmax; const uint8_t *db; const uint64_t *db_start;
+                const uint8_t *q; const uint64_t *q_start; uint32_t paths_cap; };
+// ... and what names one launch: its n candidates and their results, its work
+// counter, queue (qi 1: round 1b's stream) and whether to wait for its end
+// (false: enqueue only, nw_launch_done), the candidates' predicted rows and,
+// where the queue order is given (row_perm), perm: the candidates are
+// perm[0 .. n)
+struct NwCands { const uint32_t *cread, *csid; uint32_t n; imsame_read_result *out; uint32_t *work;
+                 const int32_t *crow = nullptr; int qi = 0; bool wait = true; const uint32_t *perm = nullptr; };
+
+static int launch_nw(imsame_ctx *c, NwPlan &pl, const NwCall &call, const NwCands &cd, double *ms) {
+    const int64_t ig = call.p->igap, eg = call.p->egap;
+    const uint32_t ymax = call.ymax, n = cd.n;
+    const int qi = cd.qi;
     hipStream_t s = qi ? c->stream_b : c->stream;
     hipEvent_t e0 = qi ? c->evb0 : c->ev0, e1 = qi ? c->evb1 : c->ev1;
     const uint64_t tb_dw = pl.tb_dw;
@@ -1548,19 +1598,19 @@ static int launch_nw(imsame_ctx *c, NwPlan &pl, const uint32_t *cread, const uin
     }
     NwLaunch P;
     memset(&P, 0, sizeof P);
-    P.db = dbp; P.db_start = dbs; P.q = qp; P.q_start = qs;
-    P.cand_read = cread; P.cand_sid = csid; P.n_cand = n;
+    P.db = call.db; P.db_start = call.db_start; P.q = call.q; P.q_start = call.q_start;
+    P.cand_read = cd.cread; P.cand_sid = cd.csid; P.n_cand = n;
     P.igap = (int32_t)ig; P.egap = (int32_t)eg;
     P.G = pl.G; P.GPW = pl.GPW; P.xcap = pl.xcap; P.xstride = pl.xstride; P.steps = pl.steps;
     P.tb = pl.np ? ao->np_tb.as<uint32_t>() : c->tb.as<uint32_t>(); P.tb_wave_dw = tb_dw;
     P.bnd = c->bnd.as<int32_t>(); P.bnd_wave = pl.bnd_dw;
     P.minlen = c->minlen.as<uint32_t>(); P.n_minlen = ymax + 1;
-    P.minident = c->minident.as<uint32_t>(); P.n_minident = xmax + ymax + 2;
-    P.counter = work;
-    P.out = outp;
+    P.minident = c->minident.as<uint32_t>(); P.n_minident = call.xmax + ymax + 2;
+    P.counter = cd.work;
+    P.out = cd.out;
     uint64_t *ctr = c->ctr.as<uint64_t>();
-    P.paths = c->paths.as<uint32_t>(); P.paths_cap = paths_cap;
-    P.paths_used = (uint32_t *)(ctr + C_PATHS); P.want_paths = p->want_paths;
+    P.paths = c->paths.as<uint32_t>(); P.paths_cap = call.paths_cap;
+    P.paths_used = (uint32_t *)(ctr + C_PATHS); P.want_paths = call.p->want_paths;
     P.flags = (uint32_t *)(ctr + C_FLAGS);
     P.ck = !(pl.two || pl.lng) ? nullptr : pl.np ? ao->np_ck.as<uint32_t>() : c->ck.as<uint32_t>();
     P.ck_wave_dw = pl.ck_dw;
@@ -1572,68 +1622,33 @@ static int launch_nw(imsame_ctx *c, NwPlan &pl, const uint32_t *cread, const uin
     P.stop_off = !(nw16_stop_env() && pl.pk && c->tab_valid && c->tab_ig == ig && c->tab_eg == eg && ymax <= c->tab_ymax &&
                    nw16_bmin(ymax, ig, eg) != INT32_MAX);
     STALL(c, s);                                 // (ahead of e0: not in the launch's time)
-    HIPCHK(hipMemsetAsync(work, 0, 4, s));
+    HIPCHK(hipMemsetAsync(cd.work, 0, 4, s));
     HIPCHK(hipEventRecord(e0, s));               // the launch's time includes its ordering
-    auto win_params = [&] {
-        const char *wu = getenv("IMSAME_NW_WIN_UP"), *wd = getenv("IMSAME_NW_WIN_DOWN");
-        P.win_up = wu ? atoi(wu) : NW16_WIN_UP; P.win_down = wd ? atoi(wd) : NW16_WIN_DOWN;
-        const char *wb = getenv("IMSAME_NW_WIN_BOTTOM");
-        P.win_bottom = wb ? atoi(wb) : NW16_WIN_BOTTOM;
-    };
-    if (perm_in) {
-        P.perm = perm_in;
-        if (crow && pl.two) { P.cand_row = crow; win_params(); }
-    } else if (crow && pl.two && n >= 64) {
-        // queue order by predicted row (first-sweep traceback windows)
-        const uint32_t nb = ((uint32_t)pl.xcap + 512) / 8 + 2;
-        DBuf &cperm = qi ? c->cperm_b : c->cperm, &rhist = qi ? c->rhist_b : c->rhist;
-        if (cperm.ensure((uint64_t)n * 4) || rhist.ensure((uint64_t)nb * 8)) return IMSAME_E_OOM;
-        uint32_t *hist = rhist.as<uint32_t>(), *cur = hist + nb;
-        HIPCHK(hipMemsetAsync(hist, 0, (size_t)nb * 4, s));
-        row_hist_kernel<<<std::min(nblk(n, 256), ROW_BLOCKS), 256, 0, s>>>(crow, n, nb, hist);
-        row_scan_kernel<<<1, 1024, 0, s>>>(hist, nb, cur);
-        row_scatter_kernel<<<std::min(nblk(n, 256), ROW_BLOCKS), 256, 0, s>>>(crow, n, nb, cur, cperm.as<uint32_t>());
-        HIPCHK(hipGetLastError());
-        P.perm = cperm.as<uint32_t>(); P.cand_row = crow;
+    // first-sweep traceback windows: a two-pass launch of candidates with
+    // predicted rows, in the given order or -- from 64 candidates -- in its
+    // own queue order by predicted row
+    P.perm = cd.perm;
+    if (cd.crow && pl.two && (cd.perm || n >= 64)) {
+        if (!cd.perm)
+            if (int rc = row_order(c, cd.crow, n, (uint32_t)pl.xcap, qi, &P.perm)) return rc;
+        P.cand_row = cd.crow;
         const char *wu = getenv("IMSAME_NW_WIN_UP"), *wd = getenv("IMSAME_NW_WIN_DOWN");
         P.win_up = wu ? atoi(wu) : NW16_WIN_UP; P.win_down = wd ? atoi(wd) : NW16_WIN_DOWN;
         const char *wb = getenv("IMSAME_NW_WIN_BOTTOM");
         P.win_bottom = wb ? atoi(wb) : NW16_WIN_BOTTOM;
     }
-    const bool k5 = pl.k == NW16_K5;
     if (pl.lp) {
         P.rlim = (int32_t)nwp_rlim(ig, eg, (uint64_t)pl.xcap, ymax);
         const char *ns = getenv("IMSAME_NWP_S");          // tests: a tiny spread drives the int32 fallback
         P.nwp_s = ns ? atoi(ns) : 0;
         P.fbk = (uint32_t *)(ctr + C_FBK);
     }
-    if (pl.lp)                         nwp_kernel<<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.lng)                   nwl_kernel<<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.mid && pl.two && pl.last4) nw16_mid_kernel<true, true><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.mid && pl.two)         nw16_mid_kernel<false, true><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.mid && pl.last4)       nw16_mid_kernel<true, false><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.mid)                   nw16_mid_kernel<false, false><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.k == NW16_K19 && pl.two) nw16_kernel<NW16_K19, true, true, NW16_K19_OFF><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.k == NW16_K19)         nw16_kernel<NW16_K19, true, false, NW16_K19_OFF><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.k == NW16_K3 && pl.two && pl.last4) nw16_kernel<NW16_K3, true, true><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.k == NW16_K3 && pl.two) nw16_kernel<NW16_K3, false, true><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.k == NW16_K3 && pl.last4) nw16_kernel<NW16_K3, true, false><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.k == NW16_K3)          nw16_kernel<NW16_K3, false, false><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.two && pl.last4 && k5) nw16_kernel<NW16_K5, true, true><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.two && k5)             nw16_kernel<NW16_K5, false, true><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.pk && pl.last4 && k5)  nw16_kernel<NW16_K5, true, false><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.pk && k5)              nw16_kernel<NW16_K5, false, false><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.two && pl.last4)       nw16_kernel<NW16_K, true, true><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.two)                   nw16_kernel<NW16_K, false, true><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.pk && pl.last4)        nw16_kernel<NW16_K, true, false><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.pk)                    nw16_kernel<NW16_K, false, false><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else if (pl.nstr > 1) nw_kernel<true><<<pl.blocks, 256, pl.lds, s>>>(P);
-    else                  nw_kernel<false><<<pl.blocks, 256, pl.lds, s>>>(P);
+    pl.row->fn<<<pl.blocks, 256, pl.lds, s>>>(P);
     HIPCHK(hipEventRecord(e1, s));
     if (wait_block()) HIPCHK(hipEventRecord(c->evw[qi ? 1 : 0][1], s));
     HIPCHK(hipGetLastError());
-    POISON_SYNC(s, pl.pk ? "nw16_kernel" : pl.lp ? "nwp_kernel" : pl.lng ? "nwl_kernel" : "nw_kernel", c);
-    return wait ? nw_launch_done(c, qi, n, ms) : 0;
+    POISON_SYNC(s, pl.row->name, c);
+    return cd.wait ? nw_launch_done(c, qi, n, ms) : 0;
 }
 
 static int paths_setup(imsame_ctx *c, const imsame_params *p, uint64_t paths_cap, uint32_t *cap32) {
@@ -1687,6 +1702,7 @@ static int rewalk_lost(imsame_ctx *c, const imsame_params *p, uint64_t read_from
     const uint64_t zero = 0;
     HIPCHK(hipMemcpyAsync(ctr + C_PATHS, &base, 8, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(ctr + C_FLAGS, &zero, 8, hipMemcpyHostToDevice, s));
+    const NwCall call = {p, ymax, xcap, c->db.as<uint8_t>(), c->db_start.as<uint64_t>(), dev_q(c), dev_qs(c), (uint32_t)cap};
     for (int cl = 0; cl < 2; ++cl) {
         const uint32_t m = (uint32_t)rd[cl].size();
         if (!m) continue;
@@ -1695,9 +1711,8 @@ static int rewalk_lost(imsame_ctx *c, const imsame_params *p, uint64_t read_from
         NwPlan pl;
         if ((rc = plan_nw(c, cl ? ycap : short_y, xcap, m, p, c->q_len_mult, &pl, true, c->q_len_uni))) return rc;
         double ms = 0;
-        rc = launch_nw(c, pl, c->cread.as<uint32_t>(), c->csid.as<uint32_t>(), m, c->cout.as<imsame_read_result>(),
-                       p->igap, p->egap, p, ymax, xcap, (uint32_t *)(ctr + C_WORK), c->db.as<uint8_t>(),
-                       c->db_start.as<uint64_t>(), dev_q(c), dev_qs(c), (uint32_t)cap, &ms);
+        rc = launch_nw(c, pl, call, {c->cread.as<uint32_t>(), c->csid.as<uint32_t>(), m, c->cout.as<imsame_read_result>(),
+                                     (uint32_t *)(ctr + C_WORK)}, &ms);
         if (rc) return rc;
         std::vector<imsame_read_result> o(m);
         HIPCHK(hipMemcpyAsync(o.data(), c->cout.p, (uint64_t)m * 64, hipMemcpyDeviceToHost, s));
@@ -1731,6 +1746,51 @@ static unsigned upd_blocks() {
 static unsigned seed_blocks() {
     static unsigned v = [] { const char *e = getenv("IMSAME_SEED_BLOCKS"); return e ? std::max(1, atoi(e)) : 1u << 30; }();
     return v;
+}
+
+// round 1b's stream and events: made at open (imsame_dev_open), here only
+// for a context that has none
+static int ensure_stream_b(imsame_ctx *c) {
+    if (c->stream_b) return 0;
+    HIPCHK(hipStreamCreateWithFlags(&c->stream_b, hipStreamNonBlocking));
+    HIPCHK(hipEventCreate(&c->evb0));
+    HIPCHK(hipEventCreate(&c->evb1));
+    for (int k = 0; k < 2; ++k)
+        HIPCHK(hipEventCreateWithFlags(&c->evw[1][k], hipEventBlockingSync | hipEventDisableTiming));
+    return 0;
+}
+
+// The per-launch form bitmasks of imsame_stats (bit k: NW launch k), once:
+// rec_launch sets them from a launch's plan, stats_append_launches moves them
+// with their launches.
+static uint64_t imsame_stats::*const LAUNCH_MASKS[] = {&imsame_stats::launch_pk,  &imsame_stats::launch_k5,
+                                                       &imsame_stats::launch_k3,  &imsame_stats::launch_np,
+                                                       &imsame_stats::launch_k19, &imsame_stats::launch_nwp};
+static void rec_launch(imsame_stats &sx, const NwPlan &pl, uint32_t nc, double ms) {
+    if (sx.nw_launches < IMSAME_LAUNCH_STATS) {
+        sx.launch_cand[sx.nw_launches] = nc;
+        sx.launch_ms[sx.nw_launches] = ms;
+        const uint64_t bit = 1ull << sx.nw_launches;
+        if (pl.pk) sx.launch_pk |= bit;
+        if (pl.pk && pl.k == NW16_K5) sx.launch_k5 |= bit;
+        if (pl.pk && pl.k == NW16_K3) sx.launch_k3 |= bit;
+        if (pl.np) sx.launch_np |= bit;
+        if (pl.pk && pl.k == NW16_K19) sx.launch_k19 |= bit;
+        if (pl.lp) sx.launch_nwp |= bit;
+    }
+    sx.ms_nw += ms; sx.nw_launches++; sx.n_nw += nc;
+}
+// src's launches (candidates, time, form bits; the first IMSAME_LAUNCH_STATS
+// of either) after dst's
+static void stats_append_launches(imsame_stats &dst, const imsame_stats &src) {
+    for (uint64_t j = 0; j < std::min<uint64_t>(src.nw_launches, IMSAME_LAUNCH_STATS); ++j) {
+        const uint64_t d = dst.nw_launches + j;
+        if (d >= IMSAME_LAUNCH_STATS) break;
+        dst.launch_cand[d] = src.launch_cand[j]; dst.launch_ms[d] = src.launch_ms[j];
+        for (auto m : LAUNCH_MASKS)
+            if ((src.*m >> j) & 1) dst.*m |= 1ull << d;
+    }
+    dst.nw_launches += src.nw_launches;
 }
 
 static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64_t n_threads_semantic,
@@ -1811,6 +1871,12 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
     const uint8_t *qd = dev_q(c);
     const uint64_t *qsd = dev_qs(c);
     uint64_t *ctr = c->ctr.as<uint64_t>();
+    // every NW launch of this call, and the plan of one of its short class
+    // (in this frame: pipeline B's thread is joined before any return behind its start)
+    const NwCall call = {p, ymax, xcap, c->db.as<uint8_t>(), c->db_start.as<uint64_t>(), qd, qsd, pcap};
+    auto plan_short = [&](uint32_t nc, NwPlan *pl) {
+        return plan_nw(c, short_y, xcap, nc, p, c->q_len_mult, pl, true, c->q_len_uni);
+    };
     HIPCHK(hipMemsetAsync(ctr, 0, C_NSLOTS * 8, s));
     const unsigned long long errinit = ~0ull;
     HIPCHK(hipMemcpyAsync(ctr + C_ERR, &errinit, 8, hipMemcpyHostToDevice, s));
@@ -1927,19 +1993,6 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
             }
             return 0;
         };
-        auto rec_launch = [&](imsame_stats &sx, const NwPlan &pl, uint32_t nc, double ms) {
-            if (sx.nw_launches < IMSAME_LAUNCH_STATS) {
-                sx.launch_cand[sx.nw_launches] = nc;
-                sx.launch_ms[sx.nw_launches] = ms;
-                if (pl.pk) sx.launch_pk |= 1ull << sx.nw_launches;
-                if (pl.pk && pl.k == NW16_K5) sx.launch_k5 |= 1ull << sx.nw_launches;
-                if (pl.pk && pl.k == NW16_K3) sx.launch_k3 |= 1ull << sx.nw_launches;
-                if (pl.np) sx.launch_np |= 1ull << sx.nw_launches;
-                if (pl.pk && pl.k == NW16_K19) sx.launch_k19 |= 1ull << sx.nw_launches;
-                if (pl.lp) sx.launch_nwp |= 1ull << sx.nw_launches;
-            }
-            sx.ms_nw += ms; sx.nw_launches++; sx.n_nw += nc;
-        };
         auto upd_launch = [&](const uint32_t *cr, const uint32_t *cs, uint32_t nc, const imsame_read_result *o,
                               uint32_t *next, int nnext_slot, hipStream_t ss, const uint32_t *uperm = nullptr) -> int {
             UpdLaunch U = {cr, cs, nc, o, read_from, c->res.as<imsame_read_result>(),
@@ -1966,13 +2019,7 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
         // one launch (tests).  IMSAME_SPLIT_ROUNDS=0 turns it off;
         // IMSAME_SPLIT_MIN sets the reads below which a round stays whole.
         if (RP.split(rnd, nact)) {
-            if (!c->stream_b) {
-                HIPCHK(hipStreamCreateWithFlags(&c->stream_b, hipStreamNonBlocking));
-                HIPCHK(hipEventCreate(&c->evb0));
-                HIPCHK(hipEventCreate(&c->evb1));
-                for (int k = 0; k < 2; ++k)
-                    HIPCHK(hipEventCreateWithFlags(&c->evw[1][k], hipEventBlockingSync | hipEventDisableTiming));
-            }
+            if ((rc = ensure_stream_b(c))) return rc;
             hipStream_t sb = c->stream_b;
             const char *sf = getenv("IMSAME_SPLIT_FRAC");            // the first half's share
             const double fa = sf ? std::max(0.05, std::min(0.95, atof(sf))) : 0.5;
@@ -2007,10 +2054,9 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
             NwPlan pla = {}, plb = {};
             double msa = 0, msb = 0;
             if (na1) {
-                if ((rc = plan_nw(c, short_y, xcap, na1, p, c->q_len_mult, &pla, true, c->q_len_uni))) return rc;
-                rc = launch_nw(c, pla, c->cread.as<uint32_t>(), c->csid.as<uint32_t>(), na1, c->cout.as<imsame_read_result>(),
-                               p->igap, p->egap, p, ymax, xcap, (uint32_t *)(ctr + C_WORK), c->db.as<uint8_t>(),
-                               c->db_start.as<uint64_t>(), qd, qsd, pcap, &msa, crow, 0, false);
+                if ((rc = plan_short(na1, &pla))) return rc;
+                rc = launch_nw(c, pla, call, {c->cread.as<uint32_t>(), c->csid.as<uint32_t>(), na1, c->cout.as<imsame_read_result>(),
+                                              (uint32_t *)(ctr + C_WORK), crow, 0, false}, &msa);
                 if (rc) return rc;
                 if ((rc = upd_launch(c->cread.as<uint32_t>(), c->csid.as<uint32_t>(), na1, c->cout.as<imsame_read_result>(),
                                      nxt, C_NNEXT, s))) return rc;
@@ -2022,19 +2068,16 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
             const uint32_t nb1 = (uint32_t)hb[0];
             bool a_done = na1 == 0;
             if (nb1) {
-                if ((rc = plan_nw(c, short_y, xcap, nb1, p, c->q_len_mult, &plb, true, c->q_len_uni))) return rc;
+                if ((rc = plan_short(nb1, &plb))) return rc;
                 // both launches share the arena only as non-persistent launches of one
                 // slot layout; otherwise the second waits for the first (as round 1b)
-                const bool same = pla.np && plb.np && plb.slot_words == pla.slot_words && plb.tb_dw == pla.tb_dw &&
-                                  plb.ck_dw == pla.ck_dw && plb.bnd_dw == pla.bnd_dw && plb.max_blocks == pla.max_blocks;
-                if (!same && !a_done) {
+                if (!np_same_layout(pla, plb) && !a_done) {
                     if ((rc = nw_launch_done(c, 0, na1, &msa))) return rc;
                     rec_launch(st, pla, na1, msa);
                     a_done = true;
                 }
-                rc = launch_nw(c, plb, Sb.cread, Sb.csid, nb1, c->cout.as<imsame_read_result>() + offB, p->igap, p->egap,
-                               p, ymax, xcap, (uint32_t *)(ctr + C_WORKB), c->db.as<uint8_t>(), c->db_start.as<uint64_t>(),
-                               qd, qsd, pcap, &msb, Sb.crow, 1, false);
+                rc = launch_nw(c, plb, call, {Sb.cread, Sb.csid, nb1, c->cout.as<imsame_read_result>() + offB,
+                                              (uint32_t *)(ctr + C_WORKB), Sb.crow, 1, false}, &msb);
                 if (rc) return rc;
                 if ((rc = upd_launch(Sb.cread, Sb.csid, nb1, c->cout.as<imsame_read_result>() + offB, nxt, C_NNEXT, sb)))
                     return rc;
@@ -2079,7 +2122,7 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
         // IMSAME_ROUND1B=0 turns it off.
         NwPlan pla = {};
         bool r1b = RP.r1b(rnd, n1, n2, hc[2]);
-        if (r1b && n1 && (rc = plan_nw(c, short_y, xcap, n1, p, c->q_len_mult, &pla, true, c->q_len_uni))) return rc;
+        if (r1b && n1 && (rc = plan_short(n1, &pla))) return rc;
         if (r1b && n1 && !pla.np) r1b = false;
         // Independent pipelines (round 6).  The reads with round-1 candidates
         // (A) and the reads round 1 paused without one (B, round 1b's scan) are
@@ -2095,13 +2138,7 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
         // budgets and visiting order per read, so the same results (tests).
         // IMSAME_PIPES=0: the joined rounds below.
         if (r1b && pipes_on(n)) {
-            if (!c->stream_b) {
-                HIPCHK(hipStreamCreateWithFlags(&c->stream_b, hipStreamNonBlocking));
-                HIPCHK(hipEventCreate(&c->evb0));
-                HIPCHK(hipEventCreate(&c->evb1));
-                for (int k = 0; k < 2; ++k)
-                    HIPCHK(hipEventCreateWithFlags(&c->evw[1][k], hipEventBlockingSync | hipEventDisableTiming));
-            }
+            if ((rc = ensure_stream_b(c))) return rc;
             hipStream_t sb = c->stream_b;
             const uint32_t npz = (uint32_t)hc[2];
             uint32_t *cr0 = c->cread.as<uint32_t>(), *cs0 = c->csid.as<uint32_t>();
@@ -2133,9 +2170,8 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
                 std::unique_lock<std::mutex> lk(c->persist_mu, std::defer_lock);
                 if (!pl.np) lk.lock();
                 double ms = 0;
-                int r = launch_nw(c, pl, cr0 + P.off, cs0 + P.off, nc, co0 + P.off, p->igap, p->egap, p, ymax, xcap,
-                                  (uint32_t *)(ctr + P.cw), c->db.as<uint8_t>(), c->db_start.as<uint64_t>(), qd, qsd,
-                                  pcap, &ms, cw_row, P.qi, true, perm);
+                int r = launch_nw(c, pl, call, {cr0 + P.off, cs0 + P.off, nc, co0 + P.off, (uint32_t *)(ctr + P.cw),
+                                                cw_row, P.qi, true, perm}, &ms);
                 if (r) return r;
                 if (lk.owns_lock()) lk.unlock();
                 rec_launch(sx, pl, nc, ms);
@@ -2171,7 +2207,7 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
                     if (nc + hp[2] == 0) break;
                     if (nc) {
                         NwPlan pl;
-                        if (int r = plan_nw(c, short_y, xcap, nc, p, c->q_len_mult, &pl, true, c->q_len_uni)) return r;
+                        if (int r = plan_short(nc, &pl)) return r;
                         if (int r = pipe_nw(P, sx, pl, nc, crow ? crow + P.off : nullptr)) return r;
                     }
                     uint64_t nn = 0;
@@ -2237,7 +2273,7 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
                         Pipe W = B;
                         W.off = 0; W.room = n1;
                         NwPlan plw;
-                        if (int r = plan_nw(c, short_y, xcap, nw, p, c->q_len_mult, &plw, true, c->q_len_uni)) return r;
+                        if (int r = plan_short(nw, &plw)) return r;
                         if (int r = pipe_nw(W, stB, plw, nw, crow, pm, c->act2.as<uint32_t>(), C_NNEXT2)) return r;
                         HIPCHK(hipEventRecord(c->ev_wd, sb));
                     }
@@ -2246,7 +2282,7 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
                     const uint32_t nb = (uint32_t)hb[0];
                     if (nb) {
                         NwPlan plb;
-                        if (int r = plan_nw(c, short_y, xcap, nb, p, c->q_len_mult, &plb, true, c->q_len_uni)) return r;
+                        if (int r = plan_short(nb, &plb)) return r;
                         if (int r = pipe_nw(B, stB, plb, nb, Sb.crow)) return r;
                     }
                     uint64_t nn = 0;
@@ -2275,8 +2311,7 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
                     fprintf(stderr, "[round 1 pipes] cand=%u unpredicted=%u paused=%u\n", n1, nw, npz);
                 if (n1 > nw) {                           // the predicted ones
                     NwPlan pls = pla;
-                    if (nw && (rc = plan_nw(c, short_y, xcap, n1 - nw, p, c->q_len_mult, &pls, true, c->q_len_uni)))
-                        return rc;
+                    if (nw && (rc = plan_short(n1 - nw, &pls))) return rc;
                     std::swap(A.act, A.nxt);             // the update writes A.nxt = act3
                     const int r = pipe_nw(A, st, pls, n1 - nw, crow, pm ? pm + nw : nullptr);
                     std::swap(A.act, A.nxt);
@@ -2302,29 +2337,12 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
             // one stats record: B's launches after A's
             st.rounds = std::max(A.rnd, B.rnd);
             st.ms_seed += stB.ms_seed;
-            for (uint64_t j = 0; j < std::min<uint64_t>(stB.nw_launches, IMSAME_LAUNCH_STATS); ++j) {
-                const uint64_t d = st.nw_launches + j;
-                if (d >= IMSAME_LAUNCH_STATS) break;
-                st.launch_cand[d] = stB.launch_cand[j]; st.launch_ms[d] = stB.launch_ms[j];
-                const uint64_t bit = 1ull << j, to = 1ull << d;
-                if (stB.launch_pk & bit) st.launch_pk |= to;
-                if (stB.launch_k5 & bit) st.launch_k5 |= to;
-                if (stB.launch_k3 & bit) st.launch_k3 |= to;
-                if (stB.launch_np & bit) st.launch_np |= to;
-                if (stB.launch_k19 & bit) st.launch_k19 |= to;
-                if (stB.launch_nwp & bit) st.launch_nwp |= to;
-            }
-            st.ms_nw += stB.ms_nw; st.nw_launches += stB.nw_launches; st.n_nw += stB.n_nw;
+            stats_append_launches(st, stB);
+            st.ms_nw += stB.ms_nw; st.n_nw += stB.n_nw;
             break;
         }
         if (r1b) {
-            if (!c->stream_b) {
-                HIPCHK(hipStreamCreateWithFlags(&c->stream_b, hipStreamNonBlocking));
-                HIPCHK(hipEventCreate(&c->evb0));
-                HIPCHK(hipEventCreate(&c->evb1));
-                for (int k = 0; k < 2; ++k)
-                    HIPCHK(hipEventCreateWithFlags(&c->evw[1][k], hipEventBlockingSync | hipEventDisableTiming));
-            }
+            if ((rc = ensure_stream_b(c))) return rc;
             hipStream_t sb = c->stream_b;
             uint32_t *act2 = c->act2.as<uint32_t>();
             const uint32_t npz = (uint32_t)hc[2];
@@ -2341,9 +2359,8 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
             if ((rc = seed_launch(Sb, npz, sb, c->evb0, c->evb1))) return rc;
             double msa = 0, msb = 0;
             if (n1) {
-                rc = launch_nw(c, pla, c->cread.as<uint32_t>(), c->csid.as<uint32_t>(), n1, c->cout.as<imsame_read_result>(),
-                               p->igap, p->egap, p, ymax, xcap, (uint32_t *)(ctr + C_WORK), c->db.as<uint8_t>(),
-                               c->db_start.as<uint64_t>(), qd, qsd, pcap, &msa, crow, 0, false);
+                rc = launch_nw(c, pla, call, {c->cread.as<uint32_t>(), c->csid.as<uint32_t>(), n1, c->cout.as<imsame_read_result>(),
+                                              (uint32_t *)(ctr + C_WORK), crow, 0, false}, &msa);
                 if (rc) return rc;
                 if ((rc = upd_launch(c->cread.as<uint32_t>(), c->csid.as<uint32_t>(), n1, c->cout.as<imsame_read_result>(),
                                      act2, C_NNEXT2, s))) return rc;
@@ -2357,21 +2374,18 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
             NwPlan plb = {};
             bool a_done = n1 == 0;
             if (nb) {
-                if ((rc = plan_nw(c, short_y, xcap, nb, p, c->q_len_mult, &plb, true, c->q_len_uni))) return rc;
+                if ((rc = plan_short(nb, &plb))) return rc;
                 // N1a's launch_nw may have fallen back to a persistent launch on
                 // this lane's own arena: then N1b must wait for it (pla.np is
                 // what it ran with)
-                const bool same = pla.np && plb.np && plb.slot_words == pla.slot_words && plb.tb_dw == pla.tb_dw &&
-                                  plb.ck_dw == pla.ck_dw && plb.bnd_dw == pla.bnd_dw && plb.max_blocks == pla.max_blocks;
-                if (!same && !a_done) {                               // not N1a's arena layout: after it
+                if (!np_same_layout(pla, plb) && !a_done) {           // not N1a's arena layout: after it
                     if ((rc = nw_launch_done(c, 0, n1, &msa))) return rc;
                     rec_launch(st, pla, n1, msa);
                     a_done = true;
                 }
-                rc = launch_nw(c, plb, c->cread.as<uint32_t>() + n1, c->csid.as<uint32_t>() + n1, nb,
-                               c->cout.as<imsame_read_result>() + n1, p->igap, p->egap, p, ymax, xcap,
-                               (uint32_t *)(ctr + C_WORKB), c->db.as<uint8_t>(), c->db_start.as<uint64_t>(), qd, qsd,
-                               pcap, &msb, Sb.crow, 1, false);
+                rc = launch_nw(c, plb, call, {c->cread.as<uint32_t>() + n1, c->csid.as<uint32_t>() + n1, nb,
+                                              c->cout.as<imsame_read_result>() + n1, (uint32_t *)(ctr + C_WORKB), Sb.crow, 1,
+                                              false}, &msb);
                 if (rc) return rc;
                 if ((rc = upd_launch(c->cread.as<uint32_t>() + n1, c->csid.as<uint32_t>() + n1, nb,
                                      c->cout.as<imsame_read_result>() + n1, act2, C_NNEXT2, sb))) return rc;
@@ -2407,9 +2421,8 @@ static int align_one(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint64
             NwPlan pl;
             if ((rc = plan_nw(c, cls[k].ylim, xcap, cls[k].n, p, c->q_len_mult, &pl, true, c->q_len_uni))) return rc;
             double ms = 0;
-            rc = launch_nw(c, pl, cls[k].cr, cls[k].cs, cls[k].n, cls[k].o, p->igap, p->egap, p, ymax, xcap,
-                           (uint32_t *)(ctr + cls[k].work), c->db.as<uint8_t>(), c->db_start.as<uint64_t>(), qd, qsd,
-                           pcap, &ms, k == 0 ? crow : nullptr);
+            rc = launch_nw(c, pl, call, {cls[k].cr, cls[k].cs, cls[k].n, cls[k].o, (uint32_t *)(ctr + cls[k].work),
+                                         k == 0 ? crow : nullptr}, &ms);
             if (rc) return rc;
             rec_launch(st, pl, cls[k].n, ms);
             if ((rc = upd_launch(cls[k].cr, cls[k].cs, cls[k].n, cls[k].o, nxt, C_NNEXT, s))) return rc;
@@ -2737,8 +2750,8 @@ static int align_impl(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint6
     imsame_stats st = S[0];
     std::vector<std::pair<float, float>> iv = c->nw_iv;
     for (int k = 1; k < nl; ++k) iv.insert(iv.end(), L[k]->nw_iv.begin(), L[k]->nw_iv.end());
-    st.nw_launches = 0; st.launch_pk = 0; st.launch_k5 = 0; st.launch_np = 0; st.launch_k19 = 0; st.launch_nwp = 0;
-    st.launch_k3 = 0;
+    st.nw_launches = 0;
+    for (auto m : LAUNCH_MASKS) st.*m = 0;
     for (int k = 0; k < np; ++k) {
         const imsame_stats &x = S[k];
         if (k) {
@@ -2751,17 +2764,7 @@ static int align_impl(imsame_ctx *c, uint64_t read_from, uint64_t read_to, uint6
             st.seed_ext_chunks += x.seed_ext_chunks; st.nw_spec_waste += x.nw_spec_waste;
             st.ms_setup = std::max(st.ms_setup, x.ms_setup); st.ms_d2h += x.ms_d2h;
         }
-        for (uint64_t j = 0; j < std::min<uint64_t>(x.nw_launches, IMSAME_LAUNCH_STATS); ++j) {
-            if (st.nw_launches + j >= IMSAME_LAUNCH_STATS) break;
-            st.launch_cand[st.nw_launches + j] = x.launch_cand[j]; st.launch_ms[st.nw_launches + j] = x.launch_ms[j];
-            if ((x.launch_pk >> j) & 1) st.launch_pk |= 1ull << (st.nw_launches + j);
-            if ((x.launch_k5 >> j) & 1) st.launch_k5 |= 1ull << (st.nw_launches + j);
-            if ((x.launch_np >> j) & 1) st.launch_np |= 1ull << (st.nw_launches + j);
-            if ((x.launch_k19 >> j) & 1) st.launch_k19 |= 1ull << (st.nw_launches + j);
-            if ((x.launch_nwp >> j) & 1) st.launch_nwp |= 1ull << (st.nw_launches + j);
-            if ((x.launch_k3 >> j) & 1) st.launch_k3 |= 1ull << (st.nw_launches + j);
-        }
-        st.nw_launches += x.nw_launches;
+        stats_append_launches(st, x);
     }
     st.nw_launch_ms = st.nw_launches ? st.ms_nw / st.nw_launches : 0;
     st.ms_nw_busy = union_ms(iv);
@@ -3041,10 +3044,11 @@ extern "C" int imsame_dev_nw_pairs(imsame_ctx *c, const uint8_t *xs, const uint6
         yuni = yuni && y_start[k + 1] - y_start[k] == ymax;
     }
     if ((rc = plan_nw(c, ymax, xmax, (uint32_t)npairs, p, ymult, &pl, false, yuni ? ymax : 0))) return rc;
+    if (getenv("IMSAME_NW_PROF")) fprintf(stderr, "[nw-kernel] %s\n", pl.row->name);     // diagnostics: the kernel of this launch
     double ms = 0;
-    rc = launch_nw(c, pl, dc.as<uint32_t>(), dc.as<uint32_t>(), (uint32_t)npairs, dout.as<imsame_read_result>(),
-                   p->igap, p->egap, p, ymax, xmax, (uint32_t *)(ctr + C_WORK), dx.as<uint8_t>(), dxs.as<uint64_t>(),
-                   dy.as<uint8_t>(), dys.as<uint64_t>(), pcap, &ms);
+    const NwCall call = {p, ymax, xmax, dx.as<uint8_t>(), dxs.as<uint64_t>(), dy.as<uint8_t>(), dys.as<uint64_t>(), pcap};
+    rc = launch_nw(c, pl, call, {dc.as<uint32_t>(), dc.as<uint32_t>(), (uint32_t)npairs, dout.as<imsame_read_result>(),
+                                 (uint32_t *)(ctr + C_WORK)}, &ms);
     if (rc) return rc;
     if (kernel_ms) *kernel_ms = ms;
     HIPCHK(hipMemcpyAsync(res, dout.p, npairs * 64, hipMemcpyDeviceToHost, s));

@@ -986,6 +986,68 @@ def test_nw16_launch_forms_equal(dev, oracle, monkeypatch):
         assert not _cmp(base[a:b], e), ((a, b), _cmp(base[a:b], e))
 
 
+def test_nw_kernel_table_rows(dev, oracle, monkeypatch, capfd):
+    """Every row of the NW kernel table (imsame_dev.hip:NW_KERNELS) through
+    Device.nw_pairs, each on 8 pairs (records cut from their read or holding
+    it, and random ones; acceptance wide open): the launch's [nw-kernel] line
+    (IMSAME_NW_PROF) names the row -- which instantiation ran, LAST and
+    19-column forms included -- and every field equals the oracle's NW.
+    Shapes, the smallest that reach each row (plan_nw): reads all 30 bases are
+    LAST for 10, 5 and 3 columns (IMSAME_NW_K), all 31 are not; all 150
+    against records <= 151 take 19 columns; all 170 / 171 the mid form, LAST /
+    not; 330 the long kernels (nwp, or nwl with IMSAME_NWP=0) and, with
+    FLAG_NW32, the int32 kernel's multi-strip form (one strip: 30 bases)."""
+    from tests.test_nw16_edges import FIELDS
+    monkeypatch.setenv("IMSAME_NW_PROF", "1")
+    monkeypatch.delenv("IMSAME_NW_K", raising=False)
+    rng = np.random.default_rng(2201)
+    rnd = lambda n: synth.ACGT[rng.integers(0, 4, n)]                 # noqa: E731
+
+    def make(ylen, xlo, xhi):
+        X, Y = [], []
+        for k in range(8):
+            y, xl = rnd(ylen), int(rng.integers(xlo, xhi + 1))
+            if k % 2:
+                x = rnd(xl)
+            elif xl <= ylen:
+                o = int(rng.integers(0, ylen - xl + 1))
+                x = y[o:o + xl]
+            else:
+                o = int(rng.integers(0, xl - ylen + 1))
+                x = np.concatenate([rnd(o), y, rnd(xl - ylen - o)])
+            X.append(x.tobytes()); Y.append(y.tobytes())
+        return X, Y, [oracle.nw(x, y, text=False) for x, y in zip(X, Y)]
+
+    sets = {30: make(30, 40, 120), 31: make(31, 40, 120), 150: make(150, 40, 120),
+            170: make(170, 100, 200), 171: make(171, 100, 200), 330: make(330, 100, 400)}
+    rows = []
+    for one in (False, True):
+        fl, ps = (FLAG_NW16_ONEPASS, "one") if one else (0, "two")
+        for ylen, last in ((30, "last,"), (31, "")):
+            for k in ("10", "5", "3"):
+                rows.append((f"nw16_kernel<{k},{last}{ps}>", ylen, {"IMSAME_NW_K": k}, fl))
+        rows.append((f"nw16_kernel<19,last,{ps}>", 150, {}, fl))
+        for ylen, last in ((170, "last,"), (171, "")):
+            rows.append((f"nw16_mid_kernel<{last}{ps}>", ylen, {}, fl))
+    rows += [("nwp_kernel", 330, {}, 0), ("nwl_kernel", 330, {"IMSAME_NWP": "0"}, 0),
+             ("nw_kernel<multi>", 330, {}, FLAG_NW32), ("nw_kernel<single>", 30, {}, FLAG_NW32)]
+    assert len({r[0] for r in rows}) == 22
+    for name, ylen, env, flags in rows:
+        X, Y, exp = sets[ylen]
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        capfd.readouterr()
+        res, _, _ = dev.nw_pairs(X, Y, dev.params(min_coverage=1e-9, min_identity=1e-9, flags=flags), want_paths=True)
+        err = capfd.readouterr().err
+        for k in env:
+            monkeypatch.delenv(k)
+        ran = [ln.split(None, 1)[1] for ln in err.splitlines() if ln.startswith("[nw-kernel] ")]
+        assert ran == [name], (name, err[-2000:])
+        for k, o in enumerate(exp):
+            for f in FIELDS:
+                assert int(res[k][f]) == int(o[f]), (name, f, k, len(X[k]))
+
+
 def test_lanes_equal_one_lane(dev, monkeypatch):
     """Three concurrent lanes (parts of a call on three streams) against one
     lane: identical per-read rows and identical .align text for every
