@@ -39,6 +39,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DEV = os.environ.get("IMSAME_LIB_DEV") or os.path.join(HERE, "lib", "libimsame_dev.so")
 LIB_HOST = os.environ.get("IMSAME_LIB_HOST") or os.path.join(HERE, "lib", "libimsame_host.so")
 CLI = os.path.join(HERE, "bin", "imsame")
+REVCOMP = os.path.join(HERE, "bin", "revComp")     # revComp IN OUT (csrc/host/imsame_revcomp.c)
 FLAG_NW32 = 1          # imsame_params.flags: force the int32 NW kernel (include/imsame_dev.h)
 FLAG_NW16 = 2          # ... or the packed int16 kernel for every launch it fits, however small
 FLAG_NW16_ONEPASS = 4  # ... the packed kernel in one pass (default: score sweep + traceback band)
@@ -95,6 +96,7 @@ def lib():
         L.imsame_dev_nw_pairs.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(Params), vp, vp, u64,
                                           C.POINTER(u64), C.POINTER(C.c_double)]
         L.imsame_dev_revcomp.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
+        abi.bind_revcomp_stream(L)
         _lib = L
     return _lib
 
@@ -396,3 +398,84 @@ class Device:
             if rc:
                 raise ImsameError(rc, "imsame_dev_revcomp")
             return out[:ol.value].tobytes()
+
+    def _revcomp_stream(self, read, in_len, write, window_bytes):
+        """imsame_dev_revcomp_stream with Python ends: read(offset, n, dst
+        address) fills the library's staging (it runs on a thread of the
+        library), write(address, n) takes the output in file order.  An
+        exception in either ends the call and is raised again here."""
+        err = []
+
+        def src(_user, offset, n, dst):
+            try:
+                read(offset, n, dst)
+                return 0
+            except BaseException as e:          # noqa: BLE001  (it must not cross the C frames)
+                err.append(e)
+                return 1
+
+        def snk(_user, p, n):
+            try:
+                write(p, n)
+                return 0
+            except BaseException as e:          # noqa: BLE001
+                err.append(e)
+                return 1
+
+        total = C.c_uint64()
+        rc = lib().imsame_dev_revcomp_stream(self._h, abi.RC_SOURCE_FN(src), None, in_len, window_bytes,
+                                             abi.RC_SINK_FN(snk), None, C.byref(total))
+        if err:
+            raise err[0]
+        if rc:
+            raise ImsameError(rc, "imsame_dev_revcomp_stream")
+        return total.value
+
+    def revcomp_stream(self, data, window_bytes=0, sink=None):
+        """reverseComplement.c on the device for images of any size, taken in
+        windows of about window_bytes (0: the library's default) from the
+        image's end: FASTA bytes -> FASTA bytes.  With sink, each piece of
+        the output goes to sink(uint8 array, valid during the call) in file
+        order and the total length is returned."""
+        src = np.frombuffer(data, dtype=np.uint8)
+        base = src.ctypes.data
+        parts = []
+
+        def read(offset, n, dst):
+            C.memmove(dst, base + offset, n)
+
+        def write(p, n):
+            piece = np.ctypeslib.as_array((C.c_uint8 * n).from_address(p))
+            if sink is None:
+                parts.append(piece.tobytes())
+            else:
+                sink(piece)
+
+        total = self._revcomp_stream(read, len(src), write, window_bytes)
+        return total if sink is not None else b"".join(parts)
+
+
+def revcomp_file(in_path, out_path, device=0, window_bytes=0):
+    """What `revComp IN OUT` does, in this process: in_path is read window by
+    window (os.preadv into the library's staging), its reverse complement
+    written to out_path as it arrives.  Returns the bytes written."""
+    fin = os.open(in_path, os.O_RDONLY)
+    try:
+        in_len = os.fstat(fin).st_size
+        with open(out_path, "wb") as fout, Device(device) as dev:
+
+            def read(offset, n, dst):
+                buf = (C.c_uint8 * n).from_address(dst)
+                got = 0
+                while got < n:
+                    r = os.preadv(fin, [memoryview(buf)[got:]], offset + got)
+                    if r <= 0:
+                        raise OSError(f"{in_path}: short read at {offset + got}")
+                    got += r
+
+            def write(p, n):
+                fout.write((C.c_uint8 * n).from_address(p))
+
+            return dev._revcomp_stream(read, in_len, write, window_bytes)
+    finally:
+        os.close(fin)

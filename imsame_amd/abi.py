@@ -15,6 +15,7 @@ IMSAME_E_ARG = -4
 IMSAME_E_RANGE = -5
 IMSAME_E_PATHS = -6
 IMSAME_E_STATE = -7
+IMSAME_E_IO = -8
 
 FIXED_K = 12
 POINT = 4
@@ -75,6 +76,17 @@ def bind_index_read(L):
     """argtypes of imsame_dev_index_read (include/imsame_dev.h)."""
     L.imsame_dev_index_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                         C.POINTER(C.c_int)]
+
+
+# imsame_rc_source / imsame_rc_sink (imsame_dev_revcomp_stream)
+RC_SOURCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)
+RC_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
+
+
+def bind_revcomp_stream(L):
+    """argtypes of imsame_dev_revcomp_stream (include/imsame_dev.h)."""
+    L.imsame_dev_revcomp_stream.argtypes = [C.c_void_p, RC_SOURCE_FN, C.c_void_p, C.c_uint64, C.c_uint64,
+                                            RC_SINK_FN, C.c_void_p, C.POINTER(C.c_uint64)]
 
 
 class Stats(C.Structure):

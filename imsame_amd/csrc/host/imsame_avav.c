@@ -156,24 +156,41 @@ static void load_fwd(mgen *m) {
     ph_parse += now_s() - t;
 }
 
+/* imsame_dev_revcomp_stream's ends: the source copies from the raw image in
+ * memory, the sink appends to a growing buffer (metagenomes of 4 GiB and
+ * more get their .r orientation this way) */
+typedef struct { uint8_t *p; uint64_t len, cap; } rc_img;
+static int rc_src(void *user, uint64_t offset, uint64_t n, uint8_t *dst) {
+    memcpy(dst, ((const mgen *)user)->raw + offset, n);
+    return 0;
+}
+static int rc_sink(void *user, const uint8_t *bytes, uint64_t n) {
+    rc_img *im = user;
+    if (im->len + n > im->cap) {
+        const uint64_t cap = im->len + n + (im->len + n) / 4;
+        uint8_t *p = realloc(im->p, cap);
+        if (!p) return 1;
+        im->p = p; im->cap = cap;
+    }
+    memcpy(im->p + im->len, bytes, n);
+    im->len += n;
+    return 0;
+}
+
 static void load_rc(mgen *m, imsame_ctx *ctx) {
     if (m->have_rc) return;
     load_raw(m);
     double t = now_s();
-    uint64_t cap = m->raw_len + m->raw_len / 64 + 4096, got = 0;
-    uint8_t *img = malloc(cap);
-    int rc = imsame_dev_revcomp(ctx, m->raw, m->raw_len, img, cap, &got);
-    if (rc == IMSAME_E_ARG && got > cap) {
-        cap = got;
-        img = realloc(img, cap);
-        rc = imsame_dev_revcomp(ctx, m->raw, m->raw_len, img, cap, &got);
-    }
+    rc_img im = {NULL, 0, m->raw_len + m->raw_len / 64 + 4096};
+    uint64_t got = 0;
+    if (!(im.p = malloc(im.cap))) die(imsame_strerror(IMSAME_E_OOM));
+    const int rc = imsame_dev_revcomp_stream(ctx, rc_src, m, m->raw_len, 0, rc_sink, &im, &got);
     if (rc) die(imsame_strerror(rc));
     ph_revcomp += now_s() - t;
     t = now_s();
-    if (host_parse_fasta_mt(img, got, 1, host_threads(), 0, &m->rc)) die("Could not parse FASTA");
+    if (host_parse_fasta_mt(im.p, got, 1, host_threads(), 0, &m->rc)) die("Could not parse FASTA");
     ph_parse += now_s() - t;
-    free(img);
+    free(im.p);
     m->have_rc = 1;
 }
 

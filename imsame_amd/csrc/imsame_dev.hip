@@ -24,6 +24,7 @@
 #include <thread>
 #include <mutex>
 #include <condition_variable>
+#include <deque>
 #include "../../include/imsame_dev.h"
 
 #include "tables.h"
@@ -306,6 +307,19 @@ struct DBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
     template <class T> T *as() const { return (T *)p; }
 };
+// page-locked host staging (imsame_dev_revcomp_stream); grows without keeping its bytes
+struct HBuf {
+    void *p = nullptr; size_t cap = 0;
+    int ensure(size_t n) {
+        if (n <= cap) return 0;
+        release();
+        n = std::max<size_t>(n, (size_t)1 << 16);
+        if (hipHostMalloc(&p, n, hipHostMallocDefault) != hipSuccess) { p = nullptr; return IMSAME_E_OOM; }
+        cap = n;
+        return 0;
+    }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+};
 
 struct imsame_ctx {
     int device = 0, ncu = 0;
@@ -390,8 +404,12 @@ struct imsame_ctx {
     double paths_hint = 0;     // path entries per read of the last call
     std::vector<uint32_t> paths_host;
     bool paths_on_host = false;
-    // revcomp
-    DBuf rc_in, rc_out, rc_a, rc_b, rc_c;
+    // revcomp: the image and the output in two sets (the stream uploads
+    // window k+1 and downloads window k-1 beside window k's kernels), scan
+    // and record scratch in one (only `stream` touches it), and the stream's
+    // page-locked staging
+    DBuf rc_in[2], rc_out[2], rc_a, rc_b, rc_c;
+    HBuf rc_hin[2], rc_hout[2];
     // database slices (imsame_dev_align_sliced): the e-value's L_DB is the
     // whole database's length, and each read scans windows below its cap
     uint64_t ev_db_len = 0;          // 0: db_len
@@ -521,6 +539,7 @@ extern "C" const char *imsame_strerror(int code) {
     case IMSAME_E_RANGE: return "gap parameters out of int32 range";
     case IMSAME_E_PATHS: return "path arena too small";
     case IMSAME_E_STATE: return "index or query not loaded";
+    case IMSAME_E_IO: return "input or output callback failed";
     }
     return "unknown error";
 }
@@ -743,11 +762,12 @@ extern "C" void imsame_dev_close(imsame_ctx *c) {
     DBuf *bufs[] = {&c->db, &c->db_start, &c->off, &c->ent, &c->brk, &c->codes, &c->fill, &c->big, &c->q,
                     &c->q_start, &c->res, &c->cur_p, &c->cur_h, &c->memo, &c->nmemo, &c->rstat, &c->act0,
                     &c->act1, &c->cread, &c->csid, &c->cread2, &c->csid2, &c->cout, &c->cout2, &c->ctr,
-                    &c->minraw, &c->minlen, &c->minident, &c->bmin, &c->tb, &c->bnd, &c->paths, &c->ck, &c->rc_in, &c->rc_out,
+                    &c->minraw, &c->minlen, &c->minident, &c->bmin, &c->tb, &c->bnd, &c->paths, &c->ck, &c->rc_in[0], &c->rc_in[1], &c->rc_out[0], &c->rc_out[1],
                     &c->rc_a, &c->rc_b, &c->rc_c, &c->cbase, &c->ccnt, &c->perr, &c->wcap, &c->wout, &c->wstart,
                     &c->crow, &c->cperm, &c->rhist, &c->act2, &c->act3, &c->slotbits, &c->np_tb, &c->np_ck, &c->dbw, &c->qw,
                     &c->cperm_b, &c->rhist_b};
     for (DBuf *b : bufs) b->release();
+    for (int k = 0; k < 2; ++k) { c->rc_hin[k].release(); c->rc_hout[k].release(); }
     (void)hipEventDestroy(c->ev0);
     (void)hipEventDestroy(c->ev1);
     if (c->evb0) (void)hipEventDestroy(c->evb0);
@@ -3078,7 +3098,98 @@ extern "C" int imsame_dev_nw_pairs(imsame_ctx *c, const uint8_t *xs, const uint6
     return ret;
 }
 
+// ---------------------------------------------------------------------------
 // reverseComplement.c:21-118 on the device (see revcomp_kernel.hip)
+// ---------------------------------------------------------------------------
+// dev_scan with the level buffers in ws (scan_ws_elems(n) entries): no
+// allocation and no host wait, so a scan queues behind other work
+static uint64_t scan_ws_elems(uint64_t n) {
+    uint64_t t = 2;
+    while (n > 1) { n = (n + 1023) / 1024; t += 2 * n; }
+    return t;
+}
+template <class TI, class TO>
+static int dev_scan_ws(hipStream_t s, const TI *in, TO *out, uint64_t n, TO *ws) {
+    if (n == 0) return 0;
+    const uint64_t nb = (n + 1023) / 1024;
+    TO *bs = ws, *bp = ws + nb;
+    scan_blocks<TI, TO><<<(unsigned)nb, 1024, 0, s>>>(in, out, bs, n);
+    if (nb > 1) {
+        int rc = dev_scan_ws<TO, TO>(s, bs, bp, nb, ws + 2 * nb);
+        if (rc) return rc;
+        scan_add<TO><<<(unsigned)nb, 1024, 0, s>>>(out, bp, n);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// An image on the device is below 4 GiB - 16 bytes (u32 positions); its
+// buffer carries RC_PAD more (the last thread's 16-byte load).
+#define RC_IMAGE_MAX 0xFFFFFF00ull
+#define RC_PAD 32
+#define RC_WINDOW_DEF (64ull << 20)        // profiles/revcomp_stream/bench.md
+#define RC_OUT_CHUNK (16ull << 20)         // the stream's download and sink unit
+
+struct RcPlan {
+    uint64_t n = 0, total = 0;
+    uint32_t nr = 0;
+    uint32_t *gpos = nullptr, *let = nullptr, *off = nullptr, *hend = nullptr;
+    uint64_t *oo = nullptr;
+};
+
+// Records, sizes and u64 output offsets of the image in[0, n) (device, on s):
+// everything up to the exact output size, which the host needs before the
+// output exists.  Waits for s twice (record and newline counts; the total).
+static int rc_measure(imsame_ctx *c, hipStream_t s, const uint8_t *in, uint64_t n, RcPlan *P) {
+    *P = RcPlan();
+    P->n = n;
+    if (n == 0) return 0;
+    const uint64_t ne = n + RC_PAD, nb = (n + 1 + RC_TILE - 1) / RC_TILE, wse = scan_ws_elems(nb + 1);
+    if (c->rc_a.ensure(ne * 4 * 2) || c->rc_b.ensure(((nb + 1) * 6 + wse) * 4 + 64)) return IMSAME_E_OOM;
+    uint32_t *gpos = c->rc_a.as<uint32_t>(), *let = gpos + ne;
+    uint32_t *bgt = c->rc_b.as<uint32_t>(), *blet = bgt + (nb + 1), *bnl = blet + (nb + 1);
+    uint32_t *pgt = bnl + (nb + 1), *plet = pgt + (nb + 1), *pnl = plet + (nb + 1), *ws = pnl + (nb + 1);
+    HIPCHK(hipMemsetAsync(bgt, 0, (nb + 1) * 3 * 4, s));        // entry nb of each: the scans' totals
+    rc_count<<<(unsigned)nb, RC_THREADS, 0, s>>>(in, n, bgt, blet, bnl);
+    int rc = dev_scan_ws(s, bgt, pgt, nb + 1, ws);
+    if (!rc) rc = dev_scan_ws(s, blet, plet, nb + 1, ws);
+    if (!rc) rc = dev_scan_ws(s, bnl, pnl, nb + 1, ws);
+    if (rc) return rc;
+    uint32_t nr = 0, nnl = 0;
+    HIPCHK(hipMemcpyAsync(&nr, pgt + nb, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&nnl, pnl + nb, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (nr == 0) return 0;
+    // off, rnl, hend, bend [nr]; szr [nr + 1]; nlpos [nnl]; then u64: oo [nr + 1] and its scan's levels
+    const uint64_t n32 = (uint64_t)nr * 5 + 1 + nnl + 2, wse64 = scan_ws_elems((uint64_t)nr + 1);
+    if (c->rc_c.ensure(n32 * 4 + ((uint64_t)nr + 1 + wse64) * 8 + 64)) return IMSAME_E_OOM;
+    if ((rc = c->rc_c.poison(s))) return rc;
+    uint32_t *off = c->rc_c.as<uint32_t>(), *rnl = off + nr, *hend = rnl + nr, *bend = hend + nr, *szr = bend + nr;
+    uint32_t *nlpos = szr + nr + 1;
+    uint64_t *oo = (uint64_t *)(off + (n32 & ~1ull)), *ws64 = oo + nr + 1;
+    rc_scan<<<(unsigned)nb, RC_THREADS, 0, s>>>(in, n, pgt, plet, pnl, gpos, let, off, rnl, nlpos);
+    rc_records<<<nblk(nr, 256), 256, 0, s>>>(n, off, rnl, nlpos, nnl, nr, gpos, let, hend, bend, szr);
+    if ((rc = dev_scan_ws<uint32_t, uint64_t>(s, szr, oo, (uint64_t)nr + 1, ws64))) return rc;
+    HIPCHK(hipMemcpyAsync(&P->total, oo + nr, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    P->nr = nr; P->gpos = gpos; P->let = let; P->off = off; P->hend = hend; P->oo = oo;
+    return 0;
+}
+
+// the write kernel of a measured image into out (P->total bytes), queued on s
+static int rc_emit(hipStream_t s, const uint8_t *in, const RcPlan *P, uint8_t *out) {
+    if (!P->nr) return 0;
+    rc_write<<<nblk(P->n, 256), 256, 0, s>>>(in, P->n, P->off, P->nr, P->hend, P->gpos, P->let, P->oo, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// One image, one call.  The output size is exact and u64: a '>' inside a
+// header opens a record that repeats the rest of that header and shares its
+// body, so the output can be far larger than the image (93,000 '>' and a
+// '\n' give 4.3 GB).  What the caller's buffer cannot take, or the call's u32
+// contract (below 2^32 - 16), is refused with *out_len set, before any byte
+// of output is written.
 extern "C" int imsame_dev_revcomp(imsame_ctx *c, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t out_cap,
                                   uint64_t *out_len) {
     if (!c || !out_len || (n && !in)) return IMSAME_E_ARG;
@@ -3087,48 +3198,225 @@ extern "C" int imsame_dev_revcomp(imsame_ctx *c, const uint8_t *in, uint64_t n, 
     hipStream_t s = c->stream;
     *out_len = 0;
     if (n == 0) return IMSAME_OK;
-    if (c->rc_in.ensure(n + 16) || c->rc_a.ensure((n + 1) * 4 * 2 + 64) || c->rc_b.ensure((n + 1) * 4 * 2 + 64))
-        return IMSAME_E_OOM;
-    uint32_t *fgt = c->rc_a.as<uint32_t>(), *flet = fgt + (n + 1);
-    uint32_t *gpos = c->rc_b.as<uint32_t>(), *let = gpos + (n + 1);
-    HIPCHK(hipMemcpyAsync(c->rc_in.p, in, n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(fgt, 0, (n + 1) * 4 * 2, s));
-    rc_flags<<<nblk(n, 256), 256, 0, s>>>(c->rc_in.as<uint8_t>(), n, fgt, flet);
-    int rc = dev_scan(s, fgt, gpos, n + 1);
-    if (!rc) rc = dev_scan(s, flet, let, n + 1);
+    if (c->rc_in[0].ensure(n + RC_PAD)) return IMSAME_E_OOM;
+    HIPCHK(hipMemcpyAsync(c->rc_in[0].p, in, n, hipMemcpyHostToDevice, s));
+    RcPlan P;
+    int rc = rc_measure(c, s, c->rc_in[0].as<uint8_t>(), n, &P);
     if (rc) return rc;
-    uint32_t nr = 0;
-    HIPCHK(hipMemcpyAsync(&nr, gpos + n, 4, hipMemcpyDeviceToHost, s));
+    if (P.nr == 0) return IMSAME_OK;
+    *out_len = P.total;
+    if (P.total > out_cap || !out || P.total >= 0xFFFFFFF0ull) return IMSAME_E_ARG;
+    if (c->rc_out[0].ensure(P.total + 16)) return IMSAME_E_OOM;
+    if ((rc = c->rc_out[0].poison(s)) || (rc = rc_emit(s, c->rc_in[0].as<uint8_t>(), &P, c->rc_out[0].as<uint8_t>())))
+        return rc;
+    HIPCHK(hipMemcpyAsync(out, c->rc_out[0].p, P.total, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (nr == 0) return IMSAME_OK;
-    // output offsets and sizes are u32: a record's output is at most its input
-    // bytes + one '\n' (headers copied, bodies lose their newlines), so the
-    // whole output is < n + nr; refuse what could wrap instead of wrapping
-    if ((uint64_t)n + nr >= 0xFFFFFFF0ull) return IMSAME_E_ARG;
-    if (c->rc_c.ensure((uint64_t)nr * 4 * 5 + 64)) return IMSAME_E_OOM;
-    if ((rc = c->rc_c.poison(s)) || (rc = c->rc_out.poison(s))) return rc;
-    uint32_t *off = c->rc_c.as<uint32_t>(), *hend = off + nr, *bend = hend + nr, *szr = bend + nr, *oo = szr + nr;
-    rc_offsets<<<nblk(n, 256), 256, 0, s>>>(c->rc_in.as<uint8_t>(), n, gpos, off);
-    rc_records<<<nblk(nr, 256), 256, 0, s>>>(c->rc_in.as<uint8_t>(), n, off, nr, let, hend, bend, szr);
-    // sizes can exceed 2^32 only for > 4 GB outputs (rejected above for inputs)
-    DBuf oo1;
-    if (oo1.ensure(((uint64_t)nr + 1) * 4)) return IMSAME_E_OOM;
-    HIPCHK(hipMemsetAsync(oo1.p, 0, ((uint64_t)nr + 1) * 4, s));
-    HIPCHK(hipMemcpyAsync(oo1.p, szr, (uint64_t)nr * 4, hipMemcpyDeviceToDevice, s));
-    if ((rc = dev_scan(s, oo1.as<uint32_t>(), oo, nr))) return rc;
-    uint32_t last_o = 0, last_sz = 0;
-    HIPCHK(hipMemcpyAsync(&last_o, oo + nr - 1, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&last_sz, szr + nr - 1, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    const uint64_t total = (uint64_t)last_o + last_sz;
-    *out_len = total;
-    if (total > out_cap || !out) return IMSAME_E_ARG;
-    if (c->rc_out.ensure(total + 16)) return IMSAME_E_OOM;
-    rc_headers<<<nblk(nr, 256), 256, 0, s>>>(c->rc_in.as<uint8_t>(), off, nr, hend, bend, let, oo, c->rc_out.as<uint8_t>());
-    rc_bodies<<<nblk(n, 256), 256, 0, s>>>(c->rc_in.as<uint8_t>(), n, off, nr, hend, bend, let, oo, c->rc_out.as<uint8_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, c->rc_out.p, total, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    oo1.release();
     return IMSAME_OK;
 }
+
+// ---- the stream ------------------------------------------------------------
+// The image is taken in windows from its end.  A reader thread fills
+// page-locked staging through the source, finds the cut ON THE HOST -- the
+// first '>' after the first '\n' of the window is a clean opener whatever
+// precedes the window, and at the start of the file the first
+// '>' -- so the next window's end is known before anything of this one
+// reaches the device, and uploads the records [cut, end) on the upload
+// stream.  A kernel thread runs the kernels of window k on the compute stream
+// (it waits twice per window, for the counts and the exact output size); the
+// calling thread downloads and sinks window k-1 in RC_OUT_CHUNK pieces on the
+// third stream meanwhile.  Buffers that cross streams and the events
+// that order them: DESIGN 12, the stream's table.
+struct RcPiece { int slot; uint64_t n; int rc; bool last; uint64_t total; };
+struct RcStream {
+    imsame_ctx *c;
+    imsame_rc_source src; void *src_user;
+    uint64_t in_len, window;
+    hipEvent_t ev_up[2], ev_k[2], ev_dn[2];   // upload done; write kernel done; chunk downloaded
+    std::mutex mu;
+    std::condition_variable cv;
+    std::deque<RcPiece> q, q2;                // uploaded windows (reader -> kernels); written ones (-> caller)
+    uint64_t launched = 0;                    // windows whose ev_k the kernel thread has recorded
+    uint64_t drained = 0;                     // windows whose output the calling thread has handed over
+    bool abort = false;
+};
+
+static int rc_read_windows(RcStream *S) {
+    imsame_ctx *c = S->c;
+    HIPCHK(hipSetDevice(c->device));
+    uint64_t e = S->in_len;
+    for (uint64_t k = 0;; ++k) {
+        const int slot = (int)(k & 1);
+        if (k >= 2) HIPCHK(hipEventSynchronize(S->ev_up[slot]));      // the staging's last upload
+        uint64_t len = std::max<uint64_t>(1, std::min<uint64_t>(S->window, RC_IMAGE_MAX)), w0 = 0, p = 0;
+        const uint8_t *h = nullptr;
+        for (;;) {                                                     // doubled until it holds a cut
+            w0 = e > len ? e - len : 0;
+            if (int rc = c->rc_hin[slot].ensure(e - w0)) return rc;
+            h = (const uint8_t *)c->rc_hin[slot].p;
+            if (S->src(S->src_user, w0, e - w0, (uint8_t *)c->rc_hin[slot].p)) return IMSAME_E_IO;
+            const uint8_t *g = nullptr;
+            if (w0 == 0) g = (const uint8_t *)memchr(h, '>', e);
+            else if (const uint8_t *nl = (const uint8_t *)memchr(h, '\n', e - w0))
+                g = (const uint8_t *)memchr(nl + 1, '>', (size_t)(h + (e - w0) - (nl + 1)));
+            if (g) { p = w0 + (uint64_t)(g - h); break; }
+            if (w0 == 0) { p = e; break; }                             // no record before e
+            if (len >= RC_IMAGE_MAX) return IMSAME_E_ARG;              // a record of 4 GiB - 16 or more
+            len = std::min<uint64_t>(len * 2, RC_IMAGE_MAX);
+        }
+        const uint64_t n = e - p;
+        if (n) {
+            if (k >= 2) {                                              // rc_in[slot]: window k-2's kernels read it
+                std::unique_lock<std::mutex> lk(S->mu);
+                S->cv.wait(lk, [&] { return S->abort || S->launched >= k - 1; });
+                if (S->abort) return IMSAME_OK;
+                lk.unlock();
+                HIPCHK(hipEventSynchronize(S->ev_k[slot]));
+            }
+            if (c->rc_in[slot].ensure(n + RC_PAD)) return IMSAME_E_OOM;
+            HIPCHK(hipMemcpyAsync(c->rc_in[slot].p, h + (p - w0), n, hipMemcpyHostToDevice, c->ustream));
+        }
+        HIPCHK(hipEventRecord(S->ev_up[slot], c->ustream));
+        const bool last = w0 == 0;
+        {
+            std::lock_guard<std::mutex> lk(S->mu);
+            if (S->abort) return IMSAME_OK;
+            S->q.push_back(RcPiece{slot, n, 0, last, 0});
+        }
+        S->cv.notify_all();
+        if (last) return IMSAME_OK;
+        e = p;
+    }
+}
+static void rc_reader(RcStream *S) {
+    const int rc = rc_read_windows(S);
+    if (rc) {
+        { std::lock_guard<std::mutex> lk(S->mu); S->q.push_back(RcPiece{0, 0, rc, true, 0}); }
+        S->cv.notify_all();
+    }
+}
+
+// download rc_out[slot][0, total) in chunks and hand them to the sink
+static int rc_drain(RcStream *S, int slot, uint64_t total, imsame_rc_sink sink, void *sink_user) {
+    imsame_ctx *c = S->c;
+    if (!total) return 0;
+    const uint64_t chunk = std::min<uint64_t>(total, RC_OUT_CHUNK), nch = (total + chunk - 1) / chunk;
+    if (c->rc_hout[0].ensure(chunk) || (nch > 1 && c->rc_hout[1].ensure(chunk))) return IMSAME_E_OOM;
+    HIPCHK(hipStreamWaitEvent(c->stream_b, S->ev_k[slot], 0));
+    auto issue = [&](uint64_t i) -> int {
+        const uint64_t a = i * chunk, m = std::min(chunk, total - a);
+        HIPCHK(hipMemcpyAsync(c->rc_hout[i & 1].p, c->rc_out[slot].as<uint8_t>() + a, m, hipMemcpyDeviceToHost,
+                              c->stream_b));
+        HIPCHK(hipEventRecord(S->ev_dn[i & 1], c->stream_b));
+        return 0;
+    };
+    if (int rc = issue(0)) return rc;
+    for (uint64_t i = 0; i < nch; ++i) {
+        if (i + 1 < nch) if (int rc = issue(i + 1)) return rc;       // its staging was sunk at i - 1
+        if (int rc = ev_wait(S->ev_dn[i & 1])) return rc;
+        if (sink(sink_user, (const uint8_t *)c->rc_hout[i & 1].p, std::min(chunk, total - i * chunk))) return IMSAME_E_IO;
+    }
+    return 0;
+}
+
+// the kernel thread: windows in the reader's order, each measured (two waits
+// for the compute stream) and written; the calling thread is left to the sink
+static int rc_kernel_windows(RcStream *S) {
+    imsame_ctx *c = S->c;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    for (uint64_t k = 0;; ++k) {
+        RcPiece pc;
+        {
+            std::unique_lock<std::mutex> lk(S->mu);
+            S->cv.wait(lk, [&] { return S->abort || !S->q.empty(); });
+            if (S->abort) return IMSAME_OK;
+            pc = S->q.front();
+            S->q.pop_front();
+        }
+        if (pc.rc) return pc.rc;
+        RcPlan P;
+        if (pc.n) {
+            HIPCHK(hipStreamWaitEvent(s, S->ev_up[pc.slot], 0));
+            if (int rc = rc_measure(c, s, c->rc_in[pc.slot].as<uint8_t>(), pc.n, &P)) return rc;
+            if (P.total) {
+                if (k >= 2) {                                          // rc_out[slot]: window k-2's output has left it
+                    std::unique_lock<std::mutex> lk(S->mu);
+                    S->cv.wait(lk, [&] { return S->abort || S->drained >= k - 1; });
+                    if (S->abort) return IMSAME_OK;
+                }
+                if (c->rc_out[pc.slot].ensure(P.total + 16)) return IMSAME_E_OOM;
+                int rc = c->rc_out[pc.slot].poison(s);
+                if (!rc) rc = rc_emit(s, c->rc_in[pc.slot].as<uint8_t>(), &P, c->rc_out[pc.slot].as<uint8_t>());
+                if (rc) return rc;
+            }
+        }
+        HIPCHK(hipEventRecord(S->ev_k[pc.slot], s));
+        pc.total = P.total;
+        {
+            std::lock_guard<std::mutex> lk(S->mu);
+            S->launched = k + 1;
+            S->q2.push_back(pc);
+        }
+        S->cv.notify_all();
+        if (pc.last) return IMSAME_OK;
+    }
+}
+static void rc_kernels(RcStream *S) {
+    const int rc = rc_kernel_windows(S);
+    if (rc) {
+        { std::lock_guard<std::mutex> lk(S->mu); S->q2.push_back(RcPiece{0, 0, rc, true, 0}); }
+        S->cv.notify_all();
+    }
+}
+
+// the calling thread: each written window's download and sink calls, in order
+static int rc_stream_run(RcStream *S, imsame_rc_sink sink, void *sink_user, uint64_t *out_len) {
+    for (uint64_t k = 0;; ++k) {
+        RcPiece pc;
+        {
+            std::unique_lock<std::mutex> lk(S->mu);
+            S->cv.wait(lk, [&] { return !S->q2.empty(); });
+            pc = S->q2.front();
+            S->q2.pop_front();
+        }
+        if (pc.rc) return pc.rc;
+        if (int rc = rc_drain(S, pc.slot, pc.total, sink, sink_user)) return rc;
+        *out_len += pc.total;
+        { std::lock_guard<std::mutex> lk(S->mu); S->drained = k + 1; }
+        S->cv.notify_all();
+        if (pc.last) return IMSAME_OK;
+    }
+}
+
+extern "C" int imsame_dev_revcomp_stream(imsame_ctx *c, imsame_rc_source src, void *src_user, uint64_t in_len,
+                                         uint64_t window_bytes, imsame_rc_sink sink, void *sink_user,
+                                         uint64_t *out_len) {
+    if (!c || !src || !sink || !out_len) return IMSAME_E_ARG;
+    if (!c->ustream || !c->stream_b) return IMSAME_E_STATE;           // a context of imsame_dev_open has both
+    *out_len = 0;
+    if (in_len == 0) return IMSAME_OK;
+    HIPCHK(hipSetDevice(c->device));
+    RcStream S;
+    S.c = c; S.src = src; S.src_user = src_user; S.in_len = in_len;
+    S.window = window_bytes ? window_bytes : RC_WINDOW_DEF;
+    hipEvent_t *evs[] = {S.ev_up, S.ev_k, S.ev_dn};
+    int nev = 0, rc = IMSAME_OK;
+    for (; nev < 6 && !rc; ++nev)
+        if (hipEventCreateWithFlags(&evs[nev / 2][nev % 2], hipEventDisableTiming) != hipSuccess) rc = IMSAME_E_HIP;
+    if (rc) --nev;
+    if (!rc) {
+        std::thread reader(rc_reader, &S), kernels(rc_kernels, &S);
+        rc = rc_stream_run(&S, sink, sink_user, out_len);
+        { std::lock_guard<std::mutex> lk(S.mu); S.abort = true; }
+        S.cv.notify_all();
+        reader.join();
+        kernels.join();
+        // nothing of this call stays queued, whatever ended it
+        const hipStream_t all[] = {c->ustream, c->stream, c->stream_b};
+        for (hipStream_t q : all)
+            if (hipStreamSynchronize(q) != hipSuccess && !rc) rc = IMSAME_E_HIP;
+    }
+    for (int k = 0; k < nev; ++k) (void)hipEventDestroy(evs[k / 2][k % 2]);
+    return rc;
+}
+

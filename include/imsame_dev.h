@@ -37,6 +37,7 @@ extern "C" {
 #define IMSAME_E_RANGE           -5   /* gap parameters could overflow int32 scores  */
 #define IMSAME_E_PATHS           -6   /* path arena too small (retry with more)      */
 #define IMSAME_E_STATE           -7   /* index / query not loaded                    */
+#define IMSAME_E_IO              -8   /* a source or sink callback returned non-zero */
 
 /* Reference constants restated (structs.h:13-19). */
 #define IMSAME_FIXED_K        12
@@ -362,9 +363,35 @@ int imsame_dev_nw_pairs(imsame_ctx *ctx, const uint8_t *xs, const uint64_t *x_st
  * order, header line kept, letters reversed and complemented (A<->T, C<->G,
  * U->A, case kept), one sequence line per record.  If out_cap is too small
  * the call returns IMSAME_E_ARG with *out_len = the size required
- * (in_len + records + 1 suffices unless headers contain '>'). */
+ * (in_len + records + 1 suffices unless headers contain '>': a '>' inside a
+ * header opens a record that repeats the rest of that header, so the exact
+ * size, a u64, can be far above in_len).  One image, one call: in_len and
+ * the output stay below 2^32 - 16 (IMSAME_E_ARG, *out_len set for the
+ * output); nothing is written before the size is known to fit. */
 int imsame_dev_revcomp(imsame_ctx *ctx, const uint8_t *in, uint64_t in_len,
                        uint8_t *out, uint64_t out_cap, uint64_t *out_len);
+
+/* The same for images of any size, streamed.  The image is taken in windows
+ * of about window_bytes (0: the default, 64 MiB) from its end towards its
+ * start; the library reads each through src into page-locked staging of its
+ * own, cuts it at a '>' that lies in no header (the first '>' after the
+ * window's first '\n'; the first '>' of the file in the first window), runs
+ * the records from the cut to the window's end and hands their output to
+ * sink, in file order, in pieces of at most 16 MiB.  A window without such a
+ * cut is doubled and read again; a record of 4 GiB - 16 bytes or more is
+ * refused (IMSAME_E_ARG).  Device and host memory follow the window, not
+ * the file -- except the output of one window, which headers that hold '>'
+ * can make larger than the window (IMSAME_E_OOM when it cannot be held).
+ *   src   fill dst with image bytes [offset, offset + n); called from a
+ *         thread of the library, one call at a time
+ *   sink  n output bytes, valid during the call; called from the calling
+ *         thread
+ * A non-zero return of either ends the call with IMSAME_E_IO.  *out_len is
+ * the total handed to sink.  The context must come from imsame_dev_open. */
+typedef int (*imsame_rc_source)(void *user, uint64_t offset, uint64_t n, uint8_t *dst);
+typedef int (*imsame_rc_sink)(void *user, const uint8_t *bytes, uint64_t n);
+int imsame_dev_revcomp_stream(imsame_ctx *ctx, imsame_rc_source src, void *src_user, uint64_t in_len,
+                              uint64_t window_bytes, imsame_rc_sink sink, void *sink_user, uint64_t *out_len);
 
 #ifdef __cplusplus
 }
