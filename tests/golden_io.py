@@ -13,19 +13,59 @@ HEADER_RE = re.compile(rb"(\(\d+, \d+\) : \d+% \d+% \d+\n \$\$\$\$\$\$\$ \n)")
 INFO_RE = re.compile(rb"^\[INFO\] (\d+ reads .*|The Jaccard-index is: .*)$", re.M)
 
 
-def nw_pairs():
-    with gzip.open(os.path.join(GOLDEN, "nw_pairs.jsonl.gz"), "rt") as f:
+def nw_pairs(stem="nw_pairs"):
+    with gzip.open(os.path.join(GOLDEN, stem + ".jsonl.gz"), "rt") as f:
         return [json.loads(l) for l in f]
 
 
-def ungapped_rows():
-    with gzip.open(os.path.join(GOLDEN, "ungapped.jsonl.gz"), "rt") as f:
+def nw_pairs_mid_long():
+    """NW rows around the kernels' switch lengths (reads of 160 .. 3000
+    columns), low-complexity sides and positive gap terms included; the
+    schema of nw_pairs() plus the row's `kind`."""
+    return nw_pairs("nw_pairs_mid_long")
+
+
+NW_FIELDS = ("score", "bx", "by", "length", "identities", "igaps", "egaps", "head_x", "head_y")
+NW_CLASSES = ("short", "mid", "long")       # reads of <= 160, 161 .. 320 and more columns: one launch each
+# the e2e cases at mid and long reads
+MID_LONG_E2E = ["mid_reads", "mid_mixed", "long_reads", "lowcomplex", "dup_records",
+                "params_strict", "params_loose", "params_gaps"]
+
+
+def nw_class(row):
+    y = len(row["Y"])
+    return NW_CLASSES[0 if y <= 160 else 1 if y <= 320 else 2]
+
+
+def nw_mid_long_groups(cls):
+    """{(igap, egap): rows} of the mid/long NW fixture's rows of one class"""
+    groups = {}
+    for r in nw_pairs_mid_long():
+        if nw_class(r) == cls:
+            groups.setdefault((r["igap"], r["egap"]), []).append(r)
+    return groups
+
+
+def mid_form_fits(ig, eg, rows):
+    """nw16_kernel.hip:nw16_fits for a launch of these rows on the 10-column form"""
+    from tests import synth
+    xmax, ymax = max(len(r["X"]) for r in rows), max(len(r["Y"]) for r in rows)
+    return ig <= 0 and eg <= 0 and ig >= synth.nw16_limit_igap(10, xmax, ymax, eg)
+
+
+def ungapped_rows(stem="ungapped"):
+    with gzip.open(os.path.join(GOLDEN, stem + ".jsonl.gz"), "rt") as f:
         rows = [json.loads(l) for l in f]
     cases = {}
     for c in sorted({r["case"] for r in rows}):
-        with gzip.open(os.path.join(GOLDEN, f"ungapped_case{c}.json.gz"), "rt") as f:
+        with gzip.open(os.path.join(GOLDEN, f"{stem}_case{c}.json.gz"), "rt") as f:
             cases[c] = json.load(f)
     return rows, cases
+
+
+def ungapped_long_rows():
+    """Walks over reads of 161-320 and 600-2500 bases, indels included."""
+    return ungapped_rows("ungapped_long")
 
 
 def seqs_arrays(strs):
@@ -39,15 +79,72 @@ def e2e_cases():
     return sorted(os.listdir(d))
 
 
+_unpacked = {}
+
+
+def _unpack(d, name):
+    """The mid- and long-read cases keep db.fa, query.fa and expected.json
+    gzipped: plain copies in a directory of this process's own."""
+    import atexit
+    import shutil
+    import tempfile
+    if name not in _unpacked:
+        if not _unpacked:
+            _unpacked[None] = tempfile.mkdtemp(prefix="imsame_golden_")
+            atexit.register(shutil.rmtree, _unpacked[None], ignore_errors=True)
+        out = os.path.join(_unpacked[None], name)
+        os.makedirs(out)
+        for f in ("db.fa", "query.fa", "expected.json"):
+            with gzip.open(os.path.join(d, f + ".gz"), "rb") as src, open(os.path.join(out, f), "wb") as dst:
+                dst.write(src.read())
+        _unpacked[name] = out
+    return _unpacked[name]
+
+
 def e2e_case(name):
     d = os.path.join(GOLDEN, "e2e", name)
-    meta = json.load(open(os.path.join(d, "expected.json")))
+    src = d if os.path.exists(os.path.join(d, "db.fa")) else _unpack(d, name)
+    meta = json.load(open(os.path.join(src, "expected.json")))
     t1 = None
     p = os.path.join(d, "T1.align.gz")
     if os.path.exists(p):
         with gzip.open(p, "rb") as f:
             t1 = f.read()
-    return dict(dir=d, db=os.path.join(d, "db.fa"), query=os.path.join(d, "query.fa"), meta=meta, t1=t1)
+    return dict(dir=d, db=os.path.join(src, "db.fa"), query=os.path.join(src, "query.fa"), meta=meta, t1=t1)
+
+
+def align_headers(blob):
+    """The (read, record, identity %, coverage %, length) of every record of an
+    .align file, sorted."""
+    return sorted(tuple(int(v) for v in re.findall(rb"\d+", h.split(b"\n")[0])) for h in HEADER_RE.findall(blob))
+
+
+def headers_of(lines):
+    """expected.json's header lines as the tuples of align_headers"""
+    return sorted(tuple(int(v) for v in re.findall(r"\d+", h)) for h in lines)
+
+
+def result_headers(res):
+    """What the .align header of every accepted row of a per-read result array
+    holds (alignmentFunctions.c:167-168): the tuples of align_headers."""
+    out = []
+    for r in range(len(res)):
+        x = res[r]
+        if x["status"] == 1:
+            L, yl = int(x["length"]), int(x["ylen"])
+            out.append((r, int(x["db_seq"]), min(100, 100 * int(x["identities"]) // L), min(100, 100 * L // yl), yl))
+    return sorted(out)
+
+
+def case_params(make, case):
+    """make(**fields) (Oracle.params, Device.params) for an e2e case's
+    command-line options; what the case does not set keeps its default."""
+    ex = case["meta"]["extra"]
+    a = dict(zip(ex[::2], ex[1::2]))
+    names = {"-evalue": ("min_e", float), "-coverage": ("min_coverage", float), "-identity": ("min_identity", float),
+             "-igap": ("igap", lambda v: -int(v)), "-egap": ("egap", lambda v: -int(v))}
+    assert set(a) <= set(names), a
+    return make(**{names[k][0]: names[k][1](v) for k, v in a.items()})
 
 
 def record_multisets(blob):

@@ -109,12 +109,7 @@ def test_nw_packed_pairs_random_vs_oracle(dev, oracle, seed, cols, monkeypatch):
 
 
 def _params_for(dev, case):
-    ex = case["meta"]["extra"]
-    if not ex:
-        return dev.params()
-    a = dict(zip(ex[::2], ex[1::2]))
-    return dev.params(min_e=float(a["-evalue"]), min_coverage=float(a["-coverage"]),
-                      min_identity=float(a["-identity"]), igap=-int(a["-igap"]), egap=-int(a["-egap"]))
+    return G.case_params(dev.params, case)      # (a case may set any subset of the options)
 
 
 @pytest.mark.parametrize("name", G.e2e_cases())

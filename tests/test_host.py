@@ -101,6 +101,44 @@ def test_emulated_nw_kernel_matches_reference_golden(emu, oracle, flags):
                 assert int(res[k][f]) == r[f], (f, ig, eg, len(r["X"]), len(r["Y"]))
 
 
+@pytest.mark.parametrize("flags", [0, imsame_amd.FLAG_NW32], ids=["auto", "nw32"])
+@pytest.mark.parametrize("cls", G.NW_CLASSES)
+def test_emulated_nw_mid_long_matches_reference_golden(emu, oracle, cls, flags):
+    """The NW kernels' source against the reference's own rows at the switch
+    lengths (tests/golden/nw_pairs_mid_long): every field, and the text
+    rendered from the kernel's path against the reference's text.  auto: the
+    packed kernel (its mid form for 161 .. 320 columns) where the range proof
+    admits the launch, the packed long-read kernel above -- read from the
+    emulator's launch counter; nw32: the int32 kernel.  Every row of the
+    fixture runs on both routes."""
+    import hashlib
+    groups = G.nw_mid_long_groups(cls)
+    assert sum(len(rs) for rs in groups.values()) == {"short": 36, "mid": 138, "long": 118}[cls]
+    nwp = emu.lib.emu_nwp_count
+    nwp.restype = C.c_uint32
+    nwp.argtypes = [C.c_void_p]
+    n_text = 0
+    for (ig, eg), rs in groups.items():
+        X, Y = [r["X"].encode() for r in rs], [r["Y"].encode() for r in rs]
+        p = oracle.params(igap=ig, egap=eg, flags=flags, want_paths=1, min_coverage=1e-9, min_identity=1e-9)
+        nwp(None)
+        rc, res, paths, fl = emu.nw_pairs(X, Y, p, paths_cap=sum(len(x) + len(y) for x, y in zip(X, Y)) + 16)
+        assert rc == 0 and fl == 0
+        ran_long = nwp(None)
+        if not flags and ig <= 0 and eg <= 0 and cls != "short":
+            assert ran_long == (0 if cls == "mid" and G.mid_form_fits(ig, eg, rs) else 1), (cls, ig, eg)
+        for k, r in enumerate(rs):
+            for f in G.NW_FIELDS:
+                assert int(res[k][f]) == r[f], (f, ig, eg, len(r["X"]), len(r["Y"]), r["kind"])
+            if res[k]["status"] == 1:
+                txt, ident = imsame_amd.render(X[k], Y[k], res[k],
+                                               paths[res[k]["path_off"]:res[k]["path_off"] + res[k]["path_len"]])
+                assert len(txt) == r["text_len"] and hashlib.sha1(txt).hexdigest() == r["text_sha1"], (ig, eg, k)
+                assert ident == r["identities"]
+                n_text += 1
+    assert n_text >= (20 if cls == "short" else 50)
+
+
 @pytest.mark.parametrize("cols", ["10", "5"])
 def test_emulated_packed_nw_mixed_shapes(emu, oracle, cols, monkeypatch):
     """nw16_kernel.hip (emulated) on launches mixing record lengths, read
@@ -583,6 +621,52 @@ def test_emulated_ungapped_matches_reference_golden(emu, oracle):
                 assert _emu_ungapped(emu, ref, rst, q3, qs3, pd0, pq0, rd, sid) == exp, (rate, rd, pq0)
                 n += 1
     assert n > 2600
+
+
+def test_emulated_ungapped_long_matches_reference_golden(emu, oracle):
+    """seed_kernel.hip:ungapped_raw on the reference's walks over reads of
+    161-320 and 600-2500 bases (tests/golden/ungapped_long: indels, seeds at
+    buffer starts, at record and read ends and more than 3 chunks deep, a
+    periodic database).  The kernel returns the raw score, which the e-value
+    is a function of: it equals the oracle's on a row whose extent and
+    e-value, bit for bit, the oracle gives as the reference recorded them."""
+    from tests.oracle_bind import UgOut
+    rows, cases = G.ungapped_long_rows()
+    arrs = {c: (G.seqs_arrays(v["db"]), G.seqs_arrays(v["reads"])) for c, v in cases.items()}
+    buf = C.create_string_buffer(64)
+    for r in rows:
+        (db, dbs), (q, qs) = arrs[r["case"]]
+        o = oracle.ungapped(db, dbs, q, qs, r["pos_db"], r["pos_q"], r["read"], r["dbseq"])
+        assert (o.x_start, o.y_start, o.t_len) == (r["x_start"], r["y_start"], r["t_len"]), r
+        oracle.lib.or_fmt_ld(C.c_void_p(C.addressof(o) + UgOut.e_value.offset), buf, 64)
+        assert buf.value.decode() == r["e_hex"], r
+        got = _emu_ungapped(emu, db, dbs, q, qs, r["pos_db"], r["pos_q"], r["read"], r["dbseq"])
+        assert got == o.raw, r
+
+
+@pytest.mark.parametrize("name", G.MID_LONG_E2E)
+def test_emulated_pipeline_matches_reference_golden(emu, oracle, name):
+    """Seed scan, rounds and NW (kernel source, emulated) on the mid- and
+    long-read e2e cases, against what the reference itself wrote: at every
+    recorded -n_threads the accepted reads and their (read, record), identity,
+    coverage and length are the golden .align headers' -- and every field of
+    every read equals the oracle's."""
+    case = G.e2e_case(name)
+    assert name in G.e2e_cases()
+    db, dbs, brk = fasta.load(case["db"], True)
+    q, qs, _ = fasta.load(case["query"])
+    assert G.align_headers(case["t1"]) == G.headers_of(case["meta"]["runs"]["1"]["headers"])
+    for T, run in case["meta"]["runs"].items():
+        rc, got, _, st = emu.align(db, dbs, q, qs, G.case_params(oracle.params, case), int(T), db_brk=brk)
+        assert rc == run["rc"] == 0
+        want = G.headers_of(run["headers"])
+        assert 0 < len(want) < len(qs)
+        assert G.result_headers(got) == want, (name, T)
+        assert np.flatnonzero(got["status"] == 1).tolist() == sorted(h[0] for h in want)
+        rc1, exp, _ = oracle.align(db, dbs, q, qs, G.case_params(oracle.params, case), int(T), brk)
+        assert rc1 == 0
+        for f in PARITY_FIELDS:
+            assert np.array_equal(got[f], exp[f]), (name, T, f)
 
 
 @pytest.mark.parametrize("flags", [0, imsame_amd.FLAG_NW32], ids=["auto", "nw32"])
